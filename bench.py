@@ -12,6 +12,12 @@ all-reduce (N>1, RCCL), SGD update with the on-device LR schedule.
   python bench.py --gpus N --steps K --warmup W
   torchrun --nproc-per-node N bench.py --gpus N ...     (the driver's launch for N > 1)
   python bench.py --impl eager                          (framework-default PyTorch eager line)
+  python bench.py ... --dump-outputs DIR                (what the last timed step computed, as DIR/*.npy)
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the result
+line.  ``--full`` is the switch for measurements beyond the headline figure that take runs of their
+own; this benchmark has none (every other configuration is a run with its own flags), so ``--full``
+runs the same steps and says so in the result line.
 
 ``python bench.py --gpus N`` started WITHOUT a torchrun environment becomes a launcher: before any
 GPU call it starts N rank processes of itself (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, rendezvous
@@ -135,6 +141,13 @@ def parse():
     ap.add_argument("--relu-logits", action="store_true", help="the reference's ReLU on the logits (D4)")
     ap.add_argument("--variant", default="",
                     help="engine path choices for A/B runs, key=0|1,... (engine/fused.py VARIANT_DEFAULTS)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: "
+                         "params (the fp32 flat weights after the step) and stats (global_step, loss, "
+                         "accuracy, lr of the step); same arguments = same inputs, run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none here: a plain run "
+                         "already is the whole benchmark)")
     return ap.parse_args()
 
 
@@ -151,6 +164,29 @@ def make_data(n, device, seed=0):
     data = torch.randint(0, 256, (n, 32, 32, 3), dtype=torch.uint8, generator=g)
     labels = torch.randint(0, 10, (n,), dtype=torch.int32, generator=g)
     return data.to(device), labels.to(device)
+
+
+DUMP_CAP_BYTES = 60 << 20      # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, eng, step_no):
+    """What a caller of the timed step holds after the last timed step: the updated fp32 weights
+    (``params.npy``, float32) and the step's published statistics (``stats.npy``, float64:
+    global_step, loss, accuracy, lr).  An output over the size cap is stored as a fixed, seeded
+    sample of its elements (in index order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = eng.flat_params().to(torch.float32).contiguous().numpy().reshape(-1)
+    if params.nbytes > DUMP_CAP_BYTES:
+        keep = np.random.default_rng(0).choice(params.size, DUMP_CAP_BYTES // params.itemsize, replace=False)
+        params = params[np.sort(keep)]
+    if hasattr(eng, "read_stats"):
+        st = eng.read_stats(step_no)
+        stats = [st["global_step"], st["loss"], st["accuracy"], st["lr"]]
+    else:
+        stats = [step_no, float(eng.last_loss), float(eng.last_acc), eng.lr(step_no - 1)]
+    np.save(os.path.join(path, "params.npy"), params)
+    np.save(os.path.join(path, "stats.npy"), np.asarray(stats, dtype=np.float64))
 
 
 def build_fused(args, info, data, labels):
@@ -289,6 +325,8 @@ def main():
             net["loss_last_step"] = round(float(eng.read_stats(device_step())["loss"]), 4)
         except Exception:
             pass
+    if args.dump_outputs and info.rank == 0:     # the replicas hold the same weights: rank 0 writes
+        dump_outputs(args.dump_outputs, eng, device_step())
     n = info.world_size
     ms = elapsed * 1000.0 / args.steps
     gbatch = args.batch * n
@@ -323,6 +361,7 @@ def main():
                 "network": net,
                 "steps_per_graph": args.steps_per_graph if capture is not None else None,
                 **({"variant": args.variant} if args.variant else {}),
+                **({"full": True} if args.full else {}),
             },
         }
         print(json.dumps(line), flush=True)

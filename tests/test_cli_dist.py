@@ -248,6 +248,37 @@ def test_bench_rejects_world_size_mismatch():
     assert out.returncode == 3, (out.returncode, out.stderr[-2000:])
 
 
+@pytest.mark.timeout(240)
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes what the last timed step computed (params.npy float32,
+    stats.npy float64); with the same arguments two runs get the same inputs, so on the CPU eager
+    path (deterministic kernels) the dumps are equal element for element.  ``--steps`` is the number
+    of timed steps (the dumped global_step proves it) and the line carries ``ms_per_step``."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--impl", "eager",
+                              "--batch", "8", "--steps", "3", "--warmup", "2", "--dataset-size", "256",
+                              "--dump-outputs", str(d)] + extra, env=env, capture_output=True, text=True, timeout=110)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        rec = lines[0]
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 8 * 1000.0 / rec["ms_per_step"]) <= 0.01 * rec["value"]
+        assert sorted(os.listdir(d)) == ["params.npy", "stats.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("params", "stats")})
+    a, b = dumps
+    assert a["params"].dtype == np.float32 and a["stats"].dtype == np.float64
+    assert a["params"].ndim == 1 and a["params"].size > 1000 and np.isfinite(a["params"]).all()
+    assert a["params"].nbytes + a["stats"].nbytes <= 64 << 20
+    assert a["stats"][0] == 2 + 3                      # warm-up + timed steps, nothing else
+    assert np.array_equal(a["params"], b["params"]) and np.array_equal(a["stats"], b["stats"])
+
+
 def test_rccl_channel_env(monkeypatch):
     """--rccl_channels sets NCCL_MIN_NCHANNELS (and a matching max) before the communicator exists;
     values already in the environment win; 0 leaves RCCL's own choice."""
