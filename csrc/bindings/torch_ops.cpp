@@ -437,17 +437,25 @@ void head(const Tensor& h1part, const Tensor& b1, const Tensor& w2t, const Tenso
   CHECK_HIP(dmlc_head(&a, stream_of(h1part)));
 }
 
-// the whole fc chain of a training step, one persistent launch (cnn_fc.hip)
-void fc_chain(const Tensor& p2, const Tensor& fc1n, const Tensor& h1part, const Tensor& b1, const Tensor& w2t,
-              const Tensor& b2, const Tensor& w3t, const Tensor& b3, const Tensor& w3d, const Tensor& labels,
-              const Tensor& idx, const c10::optional<Tensor>& counter, int64_t period, double inv_batch,
-              bool relu_logits, const Tensor& h1, const Tensor& h2, const Tensor& dl, const Tensor& dh1,
-              const Tensor& dh2, const Tensor& loss_part, const Tensor& correct_part, const Tensor& dp2,
-              const Tensor& gw1, const Tensor& gw2, const Tensor& gw3, const Tensor& gb1, const Tensor& gb2,
-              const Tensor& gb3, bool fuse_sgd, at::ArrayRef<double> sched, int64_t nvalid, const Tensor& step,
-              const c10::optional<Tensor>& step_copy, const Tensor& sync, const Tensor& err, bool dw_tasks,
-              const c10::optional<Tensor>& am2, const c10::optional<Tensor>& w2d, const c10::optional<Tensor>& dp1,
-              const c10::optional<Tensor>& dy2, const c10::optional<Tensor>& fc2n) {
+// the fc chain's arguments (fc_chain and backward_fused take the same list)
+#define DMLC_FC_PARAMS                                                                                    \
+  const Tensor &p2, const Tensor &fc1n, const Tensor &h1part, const Tensor &b1, const Tensor &w2t,          \
+      const Tensor &b2, const Tensor &w3t, const Tensor &b3, const Tensor &w3d, const Tensor &labels,       \
+      const Tensor &idx, const c10::optional<Tensor> &counter, int64_t period, double inv_batch,            \
+      bool relu_logits, const Tensor &h1, const Tensor &h2, const Tensor &dl, const Tensor &dh1,            \
+      const Tensor &dh2, const Tensor &loss_part, const Tensor &correct_part, const Tensor &dp2,            \
+      const Tensor &gw1, const Tensor &gw2, const Tensor &gw3, const Tensor &gb1, const Tensor &gb2,        \
+      const Tensor &gb3, bool fuse_sgd, at::ArrayRef<double> sched, int64_t nvalid, const Tensor &step,     \
+      const c10::optional<Tensor> &step_copy, const Tensor &sync, const Tensor &err, bool dw_tasks,         \
+      const c10::optional<Tensor> &am2, const c10::optional<Tensor> &w2d, const c10::optional<Tensor> &dp1, \
+      const c10::optional<Tensor> &dy2, const c10::optional<Tensor> &fc2n
+#define DMLC_FC_ARGS                                                                                      \
+  p2, fc1n, h1part, b1, w2t, b2, w3t, b3, w3d, labels, idx, counter, period, inv_batch, relu_logits, h1, h2, dl, \
+      dh1, dh2, loss_part, correct_part, dp2, gw1, gw2, gw3, gb1, gb2, gb3, fuse_sgd, sched, nvalid, step,       \
+      step_copy, sync, err, dw_tasks, am2, w2d, dp1, dy2, fc2n
+
+// checks the tensors and fills the chain's arguments; returns whether the conv2 dgrad (g) is on
+static bool make_fc(DMLC_FC_PARAMS, DmlcFcArgs& a, DmlcConv2DgradArgs& g) {
   const int64_t B = p2.size(0);
   TORCH_CHECK(B >= 16 && B <= 256 && B % 16 == 0, "fc_chain: batch must be a multiple of 16 in [16, 256]");
   check(p2, "p2", at::kBFloat16, {B, 2304});
@@ -485,8 +493,6 @@ void fc_chain(const Tensor& p2, const Tensor& fc1n, const Tensor& h1part, const 
   TORCH_CHECK(sched.size() == 6, "fc_chain: sched = {lr0, decay, decay_steps, staircase, warmup, grad_scale}");
   if (nvalid < 0) nvalid = B;
   TORCH_CHECK(nvalid >= 1 && nvalid <= B, "fc_chain: nvalid must be in [1, B]");
-  c10::DeviceGuard guard(p2.device());
-  DmlcFcArgs a;
   memset(&a, 0, sizeof(a));
   a.B = (int)B; a.nvalid = (int)nvalid; a.mtiles = (int)((B + 63) / 64);
   a.p2 = p2.data_ptr(); a.w1 = fc1n.data_ptr(); a.h1part = h1part.data_ptr<float>();
@@ -528,7 +534,6 @@ void fc_chain(const Tensor& p2, const Tensor& fc1n, const Tensor& h1part, const 
   const bool dg_on = am2.has_value();
   TORCH_CHECK(dg_on == w2d.has_value() && dg_on == dp1.has_value() && dg_on == dy2.has_value(),
               "fc_chain: am2, w2d, dp1, dy2 come together");
-  DmlcConv2DgradArgs g;
   memset(&g, 0, sizeof(g));
   if (dg_on) {
     check(*am2, "am2", at::kByte, {B, 6, 6, 64});
@@ -539,6 +544,15 @@ void fc_chain(const Tensor& p2, const Tensor& fc1n, const Tensor& h1part, const 
     g.dp1 = dp1->data_ptr(); g.dy2 = dy2->data_ptr(); g.B = (int)B;
     g.split = B <= 128 ? 1 : 0;          // the chain's 256 workgroups: two per image at B <= 128
   }
+  return dg_on;
+}
+
+// the whole fc chain of a training step, one persistent launch (cnn_fc.hip)
+void fc_chain(DMLC_FC_PARAMS) {
+  DmlcFcArgs a;
+  DmlcConv2DgradArgs g;
+  const bool dg_on = make_fc(DMLC_FC_ARGS, a, g);
+  c10::DeviceGuard guard(p2.device());
   CHECK_HIP(dmlc_fc_chain(&a, dg_on ? &g : nullptr, stream_of(p2)));
 }
 
@@ -686,10 +700,15 @@ void sgd(DMLC_SGD_PARAMS) {
 // Single GPU: the weight gradients AND the whole SGD step in one launch (cnn_wgrad.hip apply mode).
 // The wgrad arguments come first (data .. xraw), then the barrier words, then sgd()'s arguments
 // (whose slab tensors must be the wgrad's).
-void wgrad_sgd(const Tensor& data, const Tensor& idx, const c10::optional<Tensor>& counter, int64_t period, int64_t cy,
-               int64_t cx, const Tensor& dp1, const Tensor& am1, const Tensor& p1, const Tensor& dy2,
-               int64_t groups2, const Tensor& xraw, const Tensor& bar, DMLC_SGD_PARAMS,
-               const c10::optional<at::TensorList> fc_acts, bool fc_sgd_done, const c10::optional<at::TensorList> fp8) {
+#define DMLC_WGRAD_SGD_PARAMS                                                                              \
+  const Tensor &data, const Tensor &idx, const c10::optional<Tensor> &counter, int64_t period, int64_t cy,   \
+      int64_t cx, const Tensor &dp1, const Tensor &am1, const Tensor &p1, const Tensor &dy2,                 \
+      int64_t groups2, const Tensor &xraw, const Tensor &bar, DMLC_SGD_PARAMS,                               \
+      const c10::optional<at::TensorList> fc_acts, bool fc_sgd_done, const c10::optional<at::TensorList> fp8
+#define DMLC_WGRAD_SGD_ARGS                                                                                \
+  data, idx, counter, period, cy, cx, dp1, am1, p1, dy2, groups2, xraw, bar, DMLC_SGD_ARGS, fc_acts, fc_sgd_done, fp8
+
+static DmlcWgradArgs make_wgrad_sgd(DMLC_WGRAD_SGD_PARAMS) {
   DmlcWgradArgs a = make_wgrad(data, idx, counter, period, cy, cx, dp1, am1, part1, partb1, p1, dy2, part2, partb2,
                                groups2, xraw, fp8);
   TORCH_CHECK((mode == 0 && fc1_fused && step_rd.has_value() && roles == 0 && finalize &&
@@ -737,8 +756,34 @@ void wgrad_sgd(const Tensor& data, const Tensor& idx, const c10::optional<Tensor
     f.err = a.bar + 10 * 32;
     a.fc_in_launch = 1;
   }
+  return a;
+}
+
+void wgrad_sgd(DMLC_WGRAD_SGD_PARAMS) {
+  const DmlcWgradArgs a = make_wgrad_sgd(DMLC_WGRAD_SGD_ARGS);
   c10::DeviceGuard guard(dp1.device());
   CHECK_HIP(dmlc_wgrad(&a, stream_of(dp1)));
+}
+
+// The whole backward in one launch (cnn_bwd.hip).  A schema takes at most 64 arguments, so the launch
+// is described by two calls: backward_fused_wgrad stages wgrad_sgd's arguments (host side only, no
+// launch), backward_fused adds fc_chain's and launches once.
+static thread_local DmlcWgradArgs staged_wgrad;
+static thread_local bool staged_wgrad_set = false;
+void backward_fused_wgrad(DMLC_WGRAD_SGD_PARAMS) {
+  staged_wgrad = make_wgrad_sgd(DMLC_WGRAD_SGD_ARGS);
+  staged_wgrad_set = true;
+}
+void backward_fused(const Tensor& hand, DMLC_FC_PARAMS) {
+  TORCH_CHECK(staged_wgrad_set, "backward_fused: backward_fused_wgrad must come first");
+  staged_wgrad_set = false;
+  check_numel(hand, "hand", at::kInt, DMLC_HAND_WORDS);
+  DmlcFcArgs a;
+  DmlcConv2DgradArgs g;
+  const bool dg_on = make_fc(DMLC_FC_ARGS, a, g);
+  TORCH_CHECK(dg_on, "backward_fused: the conv2 dgrad (am2, w2d, dp1, dy2) runs in the launch");
+  c10::DeviceGuard guard(p2.device());
+  CHECK_HIP(dmlc_backward(&a, &g, &staged_wgrad, reinterpret_cast<unsigned int*>(hand.data_ptr<int>()), stream_of(p2)));
 }
 
 }  // namespace
@@ -786,6 +831,23 @@ TORCH_LIBRARY(dmlc, m) {
         "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
         "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None, "
         "Tensor[]? fc_acts=None, bool fc_sgd_done=False, Tensor[]? fp8=None) -> ()");
+  m.def("backward_fused_wgrad(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor dp1, Tensor am1, "
+        "Tensor p1, Tensor dy2, int groups2, Tensor xraw, Tensor(z!) bar, "
+        "Tensor(a!) master, Tensor(b!) grad, int mode, float grad_scale, int[] off, Tensor(r!) part1, Tensor(s!) partb1, "
+        "Tensor(t!) part2, Tensor(u!) partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
+        "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
+        "float decay_steps, bool staircase, Tensor(l!) ticket, Tensor loss_part, Tensor correct_part, "
+        "Tensor(m!) stats, Tensor(n!)? w2f8, Tensor(o!)? amax_w, Tensor(p!)? scale_w, int roles, "
+        "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
+        "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None, "
+        "Tensor[]? fc_acts=None, bool fc_sgd_done=False, Tensor[]? fp8=None) -> ()");
+  m.def("backward_fused(Tensor(w!) hand, Tensor p2, Tensor(a!) fc1n, Tensor(b!) h1part, Tensor b1, Tensor w2t, Tensor b2, "
+        "Tensor w3t, Tensor b3, Tensor w3d, Tensor labels, Tensor idx, Tensor? counter, int period, float inv_batch, "
+        "bool relu_logits, Tensor(c!) h1, Tensor(d!) h2, Tensor(e!) dl, Tensor(f!) dh1, Tensor(g!) dh2, "
+        "Tensor(h!) loss_part, Tensor(i!) correct_part, Tensor(j!) dp2, Tensor(k!) gw1, Tensor(l!) gw2, "
+        "Tensor(m!) gw3, Tensor(n!) gb1, Tensor(o!) gb2, Tensor(p!) gb3, bool fuse_sgd, float[] sched, "
+        "int nvalid, Tensor step, Tensor(q!)? step_copy, Tensor(r!) sync, Tensor(s!) err, bool dw_tasks=True, "
+        "Tensor? am2=None, Tensor? w2d=None, Tensor(t!)? dp1=None, Tensor(u!)? dy2=None, Tensor(v!)? fc2n=None) -> ()");
   m.def("sgd(Tensor(a!) master, Tensor(b!) grad, int mode, float grad_scale, int[] off, Tensor part1, Tensor partb1, "
         "Tensor part2, Tensor partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
         "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
@@ -821,4 +883,6 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("sgd", &sgd);
   m.impl("xgmi_allreduce_sgd", &xgmi_allreduce_sgd);
   m.impl("wgrad_sgd", &wgrad_sgd);
+  m.impl("backward_fused_wgrad", &backward_fused_wgrad);
+  m.impl("backward_fused", &backward_fused);
 }

@@ -324,6 +324,18 @@ hipError_t dmlc_gemm_grouped(DmlcGemmGroup* g, hipStream_t s);
 // dg: null, or the conv2 dgrad of the same batch, run in the chain's workgroups (dg->dp2 == a->dp2;
 // a->sync >= 28 * 32 words)
 hipError_t dmlc_fc_chain(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg, hipStream_t s);
+// the argument / device checks of dmlc_fc_chain and dmlc_wgrad alone (dmlc_backward runs both)
+hipError_t dmlc_fc_chain_check(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg);
+hipError_t dmlc_wgrad_check(const DmlcWgradArgs* a);
+// The whole backward of the single-GPU bf16 step in ONE launch of 256 co-resident workgroups
+// (cnn_bwd.hip; 128 < B <= 256): per block the fc chain's tasks and ticket (dmlc_fc_chain), the conv2
+// input gradient of image blockIdx, then one role of dmlc_wgrad in apply mode, fed per image through
+// the hand-off words `hand` (DMLC_HAND_WORDS zeroed uints; generation-valued, never re-armed).  Needs
+// the chain to apply every fc SGD (a->fuse_sgd == 2, w->fc_done), w->sgd.step == a->step,
+// w->w1.g1 + 4 * w->w2.g2 == 256 and no fp8 state.  Bitwise the two launches' results.
+#define DMLC_HAND_WORDS (2 * 256 * 32)
+hipError_t dmlc_backward(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg, const DmlcWgradArgs* w,
+                         unsigned int* hand, hipStream_t s);
 hipError_t dmlc_head(const DmlcHeadArgs* a, hipStream_t s);
 hipError_t dmlc_sgd(DmlcSgdArgs* a, hipStream_t s);
 

@@ -25,6 +25,9 @@
 // the last block to finish re-arms them (zero) for the next launch.
 // Every spin is bounded and sets the sticky error word (the engine's wgrad barrier error word) --
 // all 256 blocks must be co-resident (one per CU: ~150 KB of LDS each; host-checked).
+//
+// The one-launch backward (cnn_bwd.hip k_backward) includes this file with DMLC_FC_BODY_ONLY for the
+// chain's device code (fc_chain_phase: tasks + end-of-launch ticket) without k_fc_chain and its launcher.
 #include <string.h>
 
 #include "fc_common.h"
@@ -35,13 +38,13 @@ namespace dmlc {
 
 // head LDS (cnn_head.hip layouts): fc2 weights [192 n][384 k] swizzled, activations of RB rows + a
 // zero row
-constexpr int W2_LD = 384, H1_LD = 392, H2_LD = 200, DL_LD = 40;
+constexpr int HW2_LD = 384, H1_LD = 392, H2_LD = 200, DL_LD = 40;
 DEV int w2swz(int row, int col) {
-  return row * W2_LD + (((col >> 3) ^ (2 * (row & 3) + 8 * ((row >> 3) & 1))) << 3) + (col & 7);
+  return row * HW2_LD + (((col >> 3) ^ (2 * (row & 3) + 8 * ((row >> 3) & 1))) << 3) + (col & 7);
 }
 struct HL {
   static constexpr int W2 = 0;
-  static constexpr int H1 = W2 + 192 * W2_LD * 2;
+  static constexpr int H1 = W2 + 192 * HW2_LD * 2;
   static constexpr int H2 = H1 + (FC_RB + 1) * H1_LD * 2;
   static constexpr int DH2 = H2 + (FC_RB + 1) * H2_LD * 2;
   static constexpr int DL = DH2 + (FC_RB + 1) * H2_LD * 2;
@@ -130,6 +133,9 @@ DEV bf16x4 relu_mask4(const f32x4& acc, const bf16x4& h) {
                (float)h[2] > 0.f ? acc[2] : 0.f, (float)h[3] > 0.f ? acc[3] : 0.f);
 }
 
+// WT: the loss / accuracy partials are read by another block of the SAME launch (k_backward's
+// publish_step): write-through stores, drained with the hand-off rows by the publish below
+template <bool WT = false>
 DEV void head_task(const DmlcFcArgs& a, int hb, char* smem, int tid) {
   bf16* w2s = reinterpret_cast<bf16*>(smem + HL::W2);
   bf16* h1s = reinterpret_cast<bf16*>(smem + HL::H1);
@@ -278,8 +284,13 @@ DEV void head_task(const DmlcFcArgs& a, int hb, char* smem, int tid) {
     }
     const float ls = wave_sum(rowok ? loss : 0.f), cs = wave_sum(corr);
     if (lane == 0) {
-      a.loss_part[hb] = ls;
-      a.correct_part[hb] = (int)(cs + 0.5f);
+      if constexpr (WT) {
+        st_sc1(buf_rsrc(a.loss_part), (uint32_t)hb * 4, ls);
+        st_sc1(buf_rsrc(a.correct_part), (uint32_t)hb * 4, __builtin_bit_cast(float, (int)(cs + 0.5f)));
+      } else {
+        a.loss_part[hb] = ls;
+        a.correct_part[hb] = (int)(cs + 0.5f);
+      }
     }
   }
   lds_barrier();
@@ -339,22 +350,15 @@ DEV void head_task(const DmlcFcArgs& a, int hb, char* smem, int tid) {
   DMLC_STAMP(DMLC_TK_HEAD, 5);
 }
 
-
-// Each block's second phase (backward tasks, ticket, conv2 dgrad) reads its arguments through
-// late_kernarg (common.h), so the entry block loads only what the head / forward tasks need; the
-// launch epoch's load is in flight through the first phase.
-#ifdef DMLC_EAGER_ARGS                         // A/B build: every field loaded in the entry block
-#define late_fc() a
-#define late_dg() dg
-#else
-#define late_fc() late_kernarg<DmlcFcArgs>(0)
-#define late_dg() late_kernarg<DmlcConv2DgradArgs>(kernarg_second<DmlcFcArgs, DmlcConv2DgradArgs>())
-#endif
-__global__ __launch_bounds__(FT, 1) void k_fc_chain(DmlcFcArgs a, DmlcConv2DgradArgs dg) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// The chain phase of block blockIdx.x and the end-of-launch ticket; returns the launch epoch (read
+// at entry).  `a`: the kernel's by-value argument; late_fc(): the same arguments read late -- each
+// block's second phase (backward tasks, ticket) reads them through late_kernarg (common.h), so the
+// entry block loads only what the head / forward tasks need; the launch epoch's load is in flight
+// through the first phase.  WT: head_task<WT>.
+template <bool WT, class LateFc>
+DEV unsigned fc_chain_phase(const DmlcFcArgs& a, LateFc late_fc, const int64_t step, char* smem) {
   const int tid = threadIdx.x, blk = blockIdx.x;
   const int H = a.B / FC_RB;
-  const int64_t step = a.step ? *a.step : 0;   // fc1 shadow parity, LR of the fused SGD
   const int parity = (int)(step & 1);
   if (blk == 0 && tid == 0 && a.step_copy) *a.step_copy = step;
   __shared__ unsigned s_epoch;
@@ -362,7 +366,7 @@ __global__ __launch_bounds__(FT, 1) void k_fc_chain(DmlcFcArgs a, DmlcConv2Dgrad
   if (tid == 0) e0 = ld_relaxed(epochW(a));   // (in hand before this block can arrive below)
   if (blk < H) {
     // head block: its rows, then (after every head) the C tasks past the GEMM blocks' share
-    head_task(a, blk, smem, tid);
+    head_task<WT>(a, blk, smem, tid);
     if (tid == 0) s_epoch = e0;
     const DmlcFcArgs& L = late_fc();
     const int G = FC_BLOCKS - H, nc = ctask_count(L);
@@ -418,6 +422,25 @@ __global__ __launch_bounds__(FT, 1) void k_fc_chain(DmlcFcArgs a, DmlcConv2Dgrad
       __hip_atomic_store(epochW(L), epoch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+  return epoch;
+}
+
+#ifndef DMLC_FC_BODY_ONLY
+#ifdef DMLC_EAGER_ARGS                         // A/B build: every field loaded in the entry block
+#define late_fc() a
+#define late_dg() dg
+#else
+#define late_fc() late_kernarg<DmlcFcArgs>(0)
+#define late_dg() late_kernarg<DmlcConv2DgradArgs>(kernarg_second<DmlcFcArgs, DmlcConv2DgradArgs>())
+#endif
+__global__ __launch_bounds__(FT, 1) void k_fc_chain(DmlcFcArgs a, DmlcConv2DgradArgs dg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int blk = blockIdx.x;
+  const int H = a.B / FC_RB;
+  const int64_t step = a.step ? *a.step : 0;   // fc1 shadow parity, LR of the fused SGD
+  const unsigned epoch = fc_chain_phase<false>(
+      a, [&]() __attribute__((always_inline)) -> const DmlcFcArgs& { return late_fc(); }, step, smem);
+  const DmlcFcArgs& L = late_fc();
   // the conv2 input gradient of image blk (dg.B = 0: a separate launch does it): its dp2 row tile
   // comes from this launch's dp2 tasks; everything else it reads was written by earlier launches
   const DmlcConv2DgradArgs& D = late_dg();
@@ -438,16 +461,13 @@ __global__ __launch_bounds__(FT, 1) void k_fc_chain(DmlcFcArgs a, DmlcConv2Dgrad
 
 using namespace dmlc;
 
-extern "C" hipError_t dmlc_fc_chain(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg, hipStream_t s) {
+extern "C" hipError_t dmlc_fc_chain_check(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg) {
   if (a->B < 16 || a->B > 256 || a->B % 16 != 0 || a->mtiles != (a->B + 63) / 64 || !a->sync || !a->err)
     return hipErrorInvalidValue;
-  DmlcConv2DgradArgs d;
-  memset(&d, 0, sizeof(d));
   if (dg) {
     // one image per workgroup of the 256: the batch rows are the chain's, dp2 its own output
     if (dg->B != a->B || dg->dp2 != a->dp2 || !dg->am2 || !dg->wd || !dg->dp1 || !dg->dy2) return hipErrorInvalidValue;
     if (dg->split && (2 * dg->B > FC_BLOCKS || dg->B % 8)) return hipErrorInvalidValue;
-    d = *dg;
   }
   static int cus = 0;
   if (!cus) {
@@ -456,7 +476,19 @@ extern "C" hipError_t dmlc_fc_chain(const DmlcFcArgs* a, const DmlcConv2DgradArg
       return hipErrorInvalidValue;
   }
   if (cus < FC_BLOCKS) return hipErrorInvalidValue;   // every block must be co-resident (one per CU)
+  return hipSuccess;
+}
+
+extern "C" hipError_t dmlc_fc_chain(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg, hipStream_t s) {
+  const hipError_t e = dmlc_fc_chain_check(a, dg);
+  if (e != hipSuccess) return e;
+  DmlcConv2DgradArgs d;
+  memset(&d, 0, sizeof(d));
+  if (dg) d = *dg;
   DMLC_LDS_OPTIN(&k_fc_chain, FC_LDS_ALL);
   hipLaunchKernelGGL(k_fc_chain, dim3(FC_BLOCKS), dim3(FT), d.B ? FC_LDS_ALL : FC_LDS, s, *a, d);
   return hipGetLastError();
 }
+#else
+}  // namespace dmlc
+#endif  // DMLC_FC_BODY_ONLY

@@ -14,6 +14,11 @@
 //     the per-CU load rate, not the MFMA, bounded that layout.  Wave w owns taps 3w..3w+2 x the 4 co
 //     tiles (12 accumulators) and waves 0-3 also tap 24 x co tile w: 25 MFMAs per k-step on every SIMD.
 // Both: the NEXT image's global data is prefetched into registers while the current image computes.
+//
+// The one-launch backward (cnn_bwd.hip k_backward) includes this file with DMLC_WGRAD_BODY_ONLY for the
+// device code (wgrad_role: one block's role, apply mode included) without k_wgrad and its launcher; its
+// roles take dY2 / dP1 from dgrad blocks of the SAME launch (template flag INL: per-image waits on the
+// hand-off words of common.h, sc1 loads of the handed-off bytes).
 #include "w1_common.h"
 #include "sgd_common.h"
 #include "fc_common.h"
@@ -25,7 +30,9 @@ namespace dmlc {
 constexpr size_t W1_LDS = (size_t)(W1_DYT + W1_XS + 9216) * 2 + 3072 + 9216;
 static_assert(W1_FL_BYTES <= (W1_DYT + W1_XS) * 2, "flush buffer over dY1 + planes");
 
-DEV void conv1_wgrad_block(const DmlcConv1WgradArgs& a, const int grp, char* smem, bool coh = false) {
+template <bool INL = false>
+DEV void conv1_wgrad_block(const DmlcConv1WgradArgs& a, const int grp, char* smem, bool coh = false,
+                           Hand hand = Hand{nullptr, 0u, nullptr}) {
   bf16* dyt = reinterpret_cast<bf16*>(smem);
   bf16* xs = dyt + W1_DYT;
   bf16* dps = xs + W1_XS;
@@ -56,19 +63,54 @@ DEV void conv1_wgrad_block(const DmlcConv1WgradArgs& a, const int grp, char* sme
   // arrays: with the arrays in a struct hipcc kept them in scratch.
   const int cI = tid % 192, cD2 = 1024 + (tid & 127), cA1 = 512 + (tid & 63);
   uint4 vI, vD0, vD1, vD2, vA0, vA1;
-  auto load = [&](int idx, int bb) {
+  // (INL: the pool1 gradient comes from a dgrad block of this launch -- sc1 loads, after its word)
+  auto load_free = [&](int idx, int bb) {      // what no hand-off gates: the image and the argmax bytes
     const uint4* si = reinterpret_cast<const uint4*>(a.xraw ? a.xraw + (size_t)bb * 3072 : a.data + (size_t)idx * 3072);
-    const uint4* sd = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.dp1) + (size_t)bb * 9216);
     const uint4* sa = reinterpret_cast<const uint4*>(a.am1 + (size_t)bb * 9216);
     vI = si[cI];
-    vD0 = sd[tid]; vD1 = sd[tid + 512]; vD2 = sd[cD2];
     vA0 = sa[tid]; vA1 = sa[cA1];
+  };
+  auto load_dp1 = [&](int bb) {
+    if constexpr (INL) {
+      const rsrc_t r = buf_rsrc(a.dp1);
+      const uint32_t o = (uint32_t)bb * 18432u;
+      vD0 = ld16(r, o + 16u * tid); vD1 = ld16(r, o + 16u * (tid + 512)); vD2 = ld16(r, o + 16u * cD2);
+    } else {
+      const uint4* sd = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.dp1) + (size_t)bb * 9216);
+      vD0 = sd[tid]; vD1 = sd[tid + 512]; vD2 = sd[cD2];
+    }
+  };
+  auto load = [&](int idx, int bb) {
+    if constexpr (INL) {
+      load_free(idx, bb);
+      load_dp1(bb);
+    } else {                                   // (the standalone launch's load order, as it was)
+      const uint4* si = reinterpret_cast<const uint4*>(a.xraw ? a.xraw + (size_t)bb * 3072 : a.data + (size_t)idx * 3072);
+      const uint4* sd = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.dp1) + (size_t)bb * 9216);
+      const uint4* sa = reinterpret_cast<const uint4*>(a.am1 + (size_t)bb * 9216);
+      vI = si[cI];
+      vD0 = sd[tid]; vD1 = sd[tid + 512]; vD2 = sd[cD2];
+      vA0 = sa[tid]; vA1 = sa[cA1];
+    }
   };
   // with the forward's image copy (xraw) no dataset index is needed at all
   auto row_index = [&](int bb) { return a.xraw ? 0 : batch_index(a.src, a.B, bb); };
-  load(row_index(b0 < last ? b0 : last), b0 < last ? b0 : last);
+  if constexpr (INL) {
+    // the first image: everything the hand-off does not gate goes out, then one lane waits for its
+    // dP1 word (the only wait that can be exposed: later images' waits sit under an image's compute)
+    const int bf = b0 < last ? b0 : last;
+    load_free(row_index(bf), bf);
+    if (tid == 0 && b0 < a.B) hand_wait(hand, bf, HAND_DP1);
+    lds_barrier();
+    load_dp1(bf);
+  } else {
+    load(row_index(b0 < last ? b0 : last), b0 < last ? b0 : last);
+  }
   int nidx = row_index(b0 + G < last ? b0 + G : last);
   for (int b = b0; b < a.B; b += G) {
+    if constexpr (INL) {                       // image b + G's word, in front of its prefetch below
+      if (tid == 0 && b + G <= last) hand_wait(hand, b + G, HAND_DP1);
+    }
     lds_barrier();                             // previous image's MFMA reads are done
     reinterpret_cast<uint4*>(img)[cI] = vI;
     reinterpret_cast<uint4*>(dps)[tid] = vD0;
@@ -286,7 +328,9 @@ DEV void w2_fp8_main(const DmlcConv2WgradArgs& a, int c4, int grp, char* smem, f
 
 // coh: the slabs and bias partials are reduced by other blocks of the same launch (apply mode):
 // agent-coherent stores instead of streaming ones
-DEV void conv2_wgrad_block(const DmlcConv2WgradArgs& a, const int blk, const int base, char* smem, bool coh = false) {
+template <bool INL = false>
+DEV void conv2_wgrad_block(const DmlcConv2WgradArgs& a, const int blk, const int base, char* smem, bool coh = false,
+                           Hand hand = Hand{nullptr, 0u, nullptr}) {
   bf16* xt = reinterpret_cast<bf16*>(smem);
   bf16* dyt = xt + W2_XT;
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
@@ -314,12 +358,26 @@ DEV void conv2_wgrad_block(const DmlcConv2WgradArgs& a, const int blk, const int
   bf16* xdst = xt + ((xy + 2) * 16 + pxl - xy * 12 + 2) * W2_LDX + 8 * (kx & 1);
   const int kd[3] = {tid, tid + 512, 1024 + (tid & 127)};
   uint4 vx, vd[3];
-  auto load = [&](int b) {
+  // (INL: dY2 comes from a dgrad block of this launch -- sc1 loads, after its word; the input p1 is
+  // the forward launch's)
+  auto load_x = [&](int b) {
     const uint4* x = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.p1) + (size_t)b * 9216);
-    const uint4* d = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.dy2) + (size_t)b * 9216);
     vx = x[pxl * 8 + 2 * c4 + (kx & 1)];
+  };
+  auto load_dy = [&](int b) {
+    if constexpr (INL) {
+      const rsrc_t r = buf_rsrc(a.dy2);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) vd[i] = d[kd[i]];
+      for (int i = 0; i < 3; ++i) vd[i] = ld16(r, (uint32_t)b * 18432u + 16u * kd[i]);
+    } else {
+      const uint4* d = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.dy2) + (size_t)b * 9216);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) vd[i] = d[kd[i]];
+    }
+  };
+  auto load = [&](int b) {
+    load_x(b);
+    load_dy(b);
   };
 
   // per-lane pixel rows of the 5 k-steps (tr reads: rows rA = 32s + 8g + q and rB = rA + 4; input
@@ -336,8 +394,21 @@ DEV void conv2_wgrad_block(const DmlcConv2WgradArgs& a, const int blk, const int
   for (int j = 0; j < 3; ++j) toff[j] = ((3 * w + j) / 5 * 16 + (3 * w + j) % 5) * W2_LDX;
   constexpr int T24 = (4 * 16 + 4) * W2_LDX;
 
-  load(b0 < last ? b0 : last);
+  if constexpr (INL) {
+    // the first image: its input goes out, then one lane waits for its dY2 word (the only wait that
+    // can be exposed: later images' waits sit under an image's compute)
+    const int bf = b0 < last ? b0 : last;
+    load_x(bf);
+    if (tid == 0 && b0 < a.B) hand_wait(hand, bf, HAND_DY2);
+    lds_barrier();
+    load_dy(bf);
+  } else {
+    load(b0 < last ? b0 : last);
+  }
   for (int b = b0; b < a.B; b += G) {
+    if constexpr (INL) {                       // image b + G's word, in front of its prefetch below
+      if (tid == 0 && b + G <= last) hand_wait(hand, b + G, HAND_DY2);
+    }
     lds_barrier();                             // previous image's MFMA reads are done
     *reinterpret_cast<uint4*>(xdst) = vx;
 #pragma unroll
@@ -545,7 +616,13 @@ DEV void w2_chunk(const DmlcWgradArgs& A, int grp, int& b, int& m, int& e) {
 }
 DEV unsigned* w2_claim(const DmlcWgradArgs& A, int c4, int grp) { return A.bar + 11 * 32 + c4 * A.w2.g2 + grp; }
 
-DEV void conv2_apply(const DmlcWgradArgs& A, int c4, int grp, char* smem, unsigned g0, int64_t step) {
+// INL (the one-launch backward): the update below rewrites the flipped shadow w2d, which the conv2
+// dgrad of every image reads through its whole core -- and the quarter's barrier only proves that
+// every dY2 was stored, which happens BEFORE the core.  So a second wave waits, beside the barrier
+// wait, until every image's dP1 word is posted (its dgrad is over).
+template <bool INL = false>
+DEV void conv2_apply(const DmlcWgradArgs& A, int c4, int grp, char* smem, unsigned g0, int64_t step,
+                     Hand hand = Hand{nullptr, 0u, nullptr}) {
   const DmlcSgdArgs& s = A.sgd;
   const int tid = threadIdx.x, n = A.w2.g2;
   int* flag = reinterpret_cast<int*>(smem);
@@ -554,6 +631,9 @@ DEV void conv2_apply(const DmlcWgradArgs& A, int c4, int grp, char* smem, unsign
   if (tid == 0) {
     bar_arrive(wbar(A.bar, 2 + c4), wbar(A.bar, 6 + c4), g0, (unsigned)n);
     bar_wait(wbar(A.bar, 6 + c4), g0, wbar(A.bar, 10));
+  }
+  if constexpr (INL) {
+    if (tid >= 64 && tid < 128) hand_wait_all(hand, HAND_DP1, A.w2.B, tid - 64);
   }
   __syncthreads();
   DMLC_STAMP(DMLC_TK_W2, 6);
@@ -621,6 +701,12 @@ DEV void conv1_arrive(const DmlcWgradArgs& A, unsigned g0) {
   if (threadIdx.x == 0) bar_arrive(wbar(A.bar, 0), wbar(A.bar, 1), g0, (unsigned)A.w1.g1);
 }
 // arrived: the block already arrived at the conv1 barrier (conv1_arrive) and did other work since
+// INL (the one-launch backward): the stats, the step bump and the next batch rows move BEHIND the
+// barrier wait -- the head blocks that wrote the loss partials and read the labels through bidx
+// belong to this launch, and only the complete conv1 barrier proves that all of them are done (every
+// arrival needed its images' dP1, every image's dP1 its row tile's dp2, and that every head row of
+// the tile; B > 128: every block below 128 owns an image, every other block is a conv1 role).
+template <bool INL = false>
 DEV void conv1_apply(const DmlcWgradArgs& A, int grp, char* smem, unsigned g0, int64_t step, bool arrived = false) {
   const DmlcSgdArgs& s = A.sgd;
   const int tid = threadIdx.x, n = A.w1.g1;
@@ -635,15 +721,19 @@ DEV void conv1_apply(const DmlcWgradArgs& A, int grp, char* smem, unsigned g0, i
     fc_role(s, r, lr, step, lds, tid);
     lds_barrier();                             // the fc2 transpose tile is reused by the next role
   }
-  if (s.mode == 0 && grp == 0 && tid < 64) publish_step(s, step, lr, tid);
-  if (s.mode == 0 && s.bidx) {                 // no block of this launch reads bidx (xraw is set)
-    const int r = grp * W1T + tid;
-    if (r < s.bidx_n) s.bidx[r] = order_row(s.next, step + 1, r);
-  }
+  auto finish_step = [&]() __attribute__((always_inline)) {
+    if (s.mode == 0 && grp == 0 && tid < 64) publish_step<INL>(s, step, lr, tid);
+    if (s.mode == 0 && s.bidx) {               // no block of this launch reads bidx (xraw is set)
+      const int r = grp * W1T + tid;
+      if (r < s.bidx_n) s.bidx[r] = order_row(s.next, step + 1, r);
+    }
+  };
+  if constexpr (!INL) finish_step();
   DMLC_STAMP(DMLC_TK_SGD, 0);
   if (tid == 0) bar_wait(wbar(A.bar, 1), g0, wbar(A.bar, 10));
   __syncthreads();
   DMLC_STAMP(DMLC_TK_SGD, 1);
+  if constexpr (INL) finish_step();
   const int per = (1200 + n - 1) / n, ol = tid & 15, sp = tid >> 4;
   const rsrc_t part1 = buf_rsrc(A.w1.part1);
   for (int f0 = 0; f0 < per; f0 += 16) {
@@ -684,16 +774,7 @@ DEV void conv1_apply(const DmlcWgradArgs& A, int grp, char* smem, unsigned g0, i
   DMLC_STAMP(DMLC_TK_SGD, 2);
 }
 
-// The late phases (fc dW tiles, reductions + SGD, helpers, next-batch copy) read their arguments
-// through late_kernarg (common.h): the entry block loads only what the conv bodies need (same-box
-// A/B, 300 steps: B=256 3.40 -> 3.55 M img/s, B=128 2.02 -> 2.11 M; profiles/r6_late_args_ab.txt).
-#ifdef DMLC_EAGER_ARGS                         // A/B build: every field loaded in the entry block
-#define late_args() a
-#else
-#define late_args() late_kernarg<DmlcWgradArgs>(0)
-#endif
-
-// Both weight gradients in ONE launch (no stream fork/join in the step graph): blocks [0, g1) run
+// Both weight gradients in ONE launch (no stream fork/join in the step graph): roles [0, g1) run
 // the conv1 body, the next 4 * g2 the conv2 body.  One block per CU (LDS): g1 + 4 * g2 <= 256 keeps
 // every block resident in one wave of blocks.
 constexpr size_t WG_LDS = W1_LDS > W2_LDS ? W1_LDS : W2_LDS;
@@ -702,27 +783,40 @@ static_assert(WG_LDS >= (size_t)L_RED + 8 * 64 * 4 && WG_LDS >= 40960 + 64 * 136
               "the fc dW tiles reuse the weight-gradient launch's LDS");
 static_assert(W1T == FT, "the fc dW tiles run with the weight-gradient launch's block size");
 static_assert(WG_LDS >= SGD_LDS4 * 16, "apply mode reuses the block's LDS for the SGD roles");
-__global__ __launch_bounds__(W1T, 1) void k_wgrad(DmlcWgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const bool conv1 = (int)blockIdx.x < a.w1.g1;
+static_assert(W1T == W2T, "both bodies run with one block size");
+
+// Apply mode, thread 0 of role vb: the generations of its barrier (g0) and, for a conv2 helper, of the
+// quarter it helps (hg0) -- read before this block can arrive.
+DEV void wgrad_gens(const DmlcWgradArgs& a, int vb, unsigned& g0, unsigned& hg0) {
+  const bool conv1 = vb < a.w1.g1;
   int c4 = 0, grp = 0;
-  if (!conv1) w2_block_pos(a.w2, blockIdx.x - a.w1.g1, a.w1.g1, c4, grp);
-  unsigned g0 = 0, hg0 = 0;
-  int64_t step = 0;
-  const bool helper = a.apply && conv1 && w2_helpers(a) && (int)blockIdx.x < 4 * a.w2.g2;
-  if (a.apply) {                               // read before this block can arrive
-    if (threadIdx.x == 0) g0 = bar_gen(wbar(a.bar, conv1 ? 1 : 6 + c4));
-    if (helper && threadIdx.x == 0) {
-      int hc4, hgrp;
-      w2_block_pos(a.w2, blockIdx.x, a.w1.g1, hc4, hgrp);
-      hg0 = bar_gen(wbar(a.bar, 6 + hc4));
-    }
-    step = *a.sgd.step_rd;
+  if (!conv1) w2_block_pos(a.w2, vb - a.w1.g1, a.w1.g1, c4, grp);
+  const bool helper = a.apply && conv1 && w2_helpers(a) && vb < 4 * a.w2.g2;
+  g0 = bar_gen(wbar(a.bar, conv1 ? 1 : 6 + c4));
+  if (helper) {
+    int hc4, hgrp;
+    w2_block_pos(a.w2, vb, a.w1.g1, hc4, hgrp);
+    hg0 = bar_gen(wbar(a.bar, 6 + hc4));
   }
+}
+
+// Role vb of the launch's g1 + 4 * g2 (k_wgrad: vb = blockIdx.x).  `a`: the arguments the conv bodies
+// read; late_args(): the same arguments read late -- the late phases (fc dW tiles, reductions + SGD,
+// helpers, next-batch copy) read them through late_kernarg (common.h), so the entry block loads only
+// what the conv bodies need (same-box A/B, 300 steps: B=256 3.40 -> 3.55 M img/s, B=128 2.02 -> 2.11 M;
+// profiles/r6_late_args_ab.txt).  g0 / hg0: wgrad_gens (thread 0); step: the step this launch applies.
+// INL: see the top of this file (apply mode without fc tiles or fc SGD roles only).
+template <bool INL, class LateArgs>
+DEV void wgrad_role(const DmlcWgradArgs& a, LateArgs late_args, const int vb, char* smem, unsigned g0, unsigned hg0,
+                    const int64_t step, Hand hand = Hand{nullptr, 0u, nullptr}) {
+  const bool conv1 = vb < a.w1.g1;
+  int c4 = 0, grp = 0;
+  if (!conv1) w2_block_pos(a.w2, vb - a.w1.g1, a.w1.g1, c4, grp);
+  const bool helper = a.apply && conv1 && w2_helpers(a) && vb < 4 * a.w2.g2;
   if (conv1) {
-    conv1_wgrad_block(a.w1, blockIdx.x, smem, a.apply != 0);
+    conv1_wgrad_block<INL>(a.w1, vb, smem, a.apply != 0, hand);
     const DmlcWgradArgs& L = late_args();
-    if (a.apply && L.fc_in_launch) {
+    if (!INL && a.apply && L.fc_in_launch) {
       // arrive at the conv1 barrier, then the fc weight gradients + their SGD (inputs from earlier
       // launches: no waits) while the rest of the family arrives, then the conv1 reduction + SGD;
       // the conv2 help comes last, when the conv2 slabs are ready anyway (running the fc tiles
@@ -730,33 +824,51 @@ __global__ __launch_bounds__(W1T, 1) void k_wgrad(DmlcWgradArgs a) {
       // (the first task's operand loads go out before the slab stores are drained: the arrival
       // waits for both at once)
       const int parity = (int)(step & 1);
-      if (blockIdx.x >= FC_DW_TASKS) conv1_arrive(L, g0);
-      for (int d = blockIdx.x; d < FC_DW_TASKS; d += L.w1.g1) {
+      if (vb >= FC_DW_TASKS) conv1_arrive(L, g0);
+      for (int d = vb; d < FC_DW_TASKS; d += L.w1.g1) {
         const CTask T = dw_ctask(d);
         PreRegs R;
         pre_issue(L.fc, T, parity, R, threadIdx.x);
-        const bool first = d == (int)blockIdx.x;
+        const bool first = d == vb;
         dw_task<false>(L.fc, T, R, step, smem, threadIdx.x, [&]() {
           if (first) conv1_arrive(L, g0);
         });
       }
       DMLC_STAMP(DMLC_TK_SGD, 3);
-      conv1_apply(L, blockIdx.x, smem, g0, step, true);
+      conv1_apply(L, vb, smem, g0, step, true);
     } else if (a.apply) {
-      conv1_apply(L, blockIdx.x, smem, g0, step);
+      conv1_apply<INL>(L, vb, smem, g0, step);
     }
-    if (helper) conv2_help(L, blockIdx.x, smem, hg0, step);
+    if (helper) conv2_help(L, vb, smem, hg0, step);
     // the next step's raw images over xraw: every conv1 block passed the conv1 barrier after its
     // image loop, so no block of this launch reads xraw any more
     if (a.apply && L.sgd.mode == 0 && L.sgd.xnext)
-      for (int r = blockIdx.x; r < L.sgd.bidx_n; r += L.w1.g1) copy_next_row(L.sgd, step, r, threadIdx.x);
+      for (int r = vb; r < L.sgd.bidx_n; r += L.w1.g1) copy_next_row(L.sgd, step, r, threadIdx.x);
     DMLC_STAMP(DMLC_TK_SGD, 4);
   } else {
-    conv2_wgrad_block(a.w2, blockIdx.x - a.w1.g1, a.w1.g1, smem, a.apply != 0);
-    if (a.apply) conv2_apply(late_args(), c4, grp, smem, g0, step);
+    conv2_wgrad_block<INL>(a.w2, vb - a.w1.g1, a.w1.g1, smem, a.apply != 0, hand);
+    if (a.apply) conv2_apply<INL>(late_args(), c4, grp, smem, g0, step, hand);
   }
 }
-static_assert(W1T == W2T, "k_wgrad runs both bodies with one block size");
+
+#ifndef DMLC_WGRAD_BODY_ONLY
+#ifdef DMLC_EAGER_ARGS                         // A/B build: every field loaded in the entry block
+#define late_args() a
+#else
+#define late_args() late_kernarg<DmlcWgradArgs>(0)
+#endif
+
+__global__ __launch_bounds__(W1T, 1) void k_wgrad(DmlcWgradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned g0 = 0, hg0 = 0;
+  int64_t step = 0;
+  if (a.apply) {                               // read before this block can arrive
+    if (threadIdx.x == 0) wgrad_gens(a, blockIdx.x, g0, hg0);
+    step = *a.sgd.step_rd;
+  }
+  wgrad_role<false>(a, [&]() __attribute__((always_inline)) -> const DmlcWgradArgs& { return late_args(); },
+                    blockIdx.x, smem, g0, hg0, step);
+}
 
 }  // namespace dmlc
 
@@ -764,9 +876,7 @@ using namespace dmlc;
 
 extern "C" {
 
-hipError_t dmlc_wgrad(const DmlcWgradArgs* a, hipStream_t s) {
-  DMLC_LDS_OPTIN(&k_wgrad, WG_LDS);
-  const int blocks = a->w1.g1 + 4 * a->w2.g2;
+hipError_t dmlc_wgrad_check(const DmlcWgradArgs* a) {
   if (a->apply) {
     // every barrier family must fit on the chip at once (one block per CU), fp32 slabs, the step
     // read from the head's copy (a block bumps *step while others may not have read it yet), and
@@ -790,8 +900,19 @@ hipError_t dmlc_wgrad(const DmlcWgradArgs* a, hipStream_t s) {
         g.part2 != a->w2.part2 || g.g1 != a->w1.g1 || g.g2 != a->w2.g2 || g.bidx_n > a->w1.g1 * W1T)
       return hipErrorInvalidValue;
   }
+  return hipSuccess;
+}
+
+hipError_t dmlc_wgrad(const DmlcWgradArgs* a, hipStream_t s) {
+  DMLC_LDS_OPTIN(&k_wgrad, WG_LDS);
+  const int blocks = a->w1.g1 + 4 * a->w2.g2;
+  const hipError_t e = dmlc_wgrad_check(a);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_wgrad, dim3(blocks), dim3(W1T), WG_LDS, s, *a);
   return hipGetLastError();
 }
 
 }  // extern "C"
+#else
+}  // namespace dmlc
+#endif  // DMLC_WGRAD_BODY_ONLY

@@ -281,6 +281,48 @@ DEV void seam_wait(const Seam& s, int lane, unsigned* err, unsigned errbit, int 
   }
 }
 
+// Per-image hand-off words of the one-launch backward (cnn_bwd.hip): word (b, k) -- k = 0 "dY2 of
+// image b stored", k = 1 "dP1 of image b stored" -- each on its own 128-B line.  Generation-valued:
+// the producer stores gen = launch epoch + 1 and the consumer waits for exactly that value, so nothing
+// is re-armed and a wait that gave up leaves nothing raised.  Producer (the valid form of fc_common.h
+// publish): write-through stores, every storing wave drains, the workgroup barriers, ONE lane posts.
+// Consumer: one lane (or one wave, hand_wait_all) polls, the workgroup barriers, every load of the
+// handed-off bytes is an sc1 buffer load.  Bounded; on give-up bit 2 of the sticky error word is set.
+constexpr int HAND_DY2 = 0, HAND_DP1 = 1;
+struct Hand { unsigned* w; unsigned gen; unsigned* err; };
+DEV unsigned* hand_word(const Hand& h, int b, int k) { return h.w + 32 * (2 * b + k); }
+DEV void hand_post(const Hand& h, int b, int k) {
+  __hip_atomic_store(hand_word(h, b, k), h.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV void hand_wait(const Hand& h, int b, int k) {
+  unsigned* p = hand_word(h, b, k);
+  for (unsigned it = 0; __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != h.gen; ++it) {
+    if (it >= DMLC_SPIN_LIMIT) {
+      __hip_atomic_fetch_or(h.err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+// every image b < B (<= 256) posted word k: call with all 64 lanes of one wave
+DEV void hand_wait_all(const Hand& h, int k, int B, int lane) {
+  for (unsigned it = 0;; ++it) {
+    bool ok = true;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int b = lane + 64 * u;
+      const unsigned v = __hip_atomic_load(hand_word(h, b < B ? b : 0, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ok = ok && (b >= B || v == h.gen);
+    }
+    if (__all(ok)) break;
+    if (it >= DMLC_SPIN_LIMIT) {
+      if (lane == 0) __hip_atomic_fetch_or(h.err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+
 // 32-bit integer mixer (a bijective avalanche hash): the round function of the data-order Feistel
 // network below.  Host twin: dmlc/data/order.py (_mix32).
 DEV uint32_t mix32(uint32_t x) {

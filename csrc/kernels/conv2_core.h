@@ -64,9 +64,14 @@ DEV void ws_put(bf16* buf, int w, int lane, Slice5 v) {
 // of the 36 units -- the earlier 2-3 pixel tiles x 2 c_out tiles per wave put 10 on two SIMDs and 8
 // on the other two.  Every output tile is still summed by one wave in the same k order, so the
 // results are bit-identical to that tiling.
+// post: null, or the hand-off word this workgroup posts (value post_gen) once the core's first
+// barrier has passed -- the caller's write-through stores issued before the core (the dgrad's dY2) are
+// then drained by every wave at a point where the core waits for vmcnt(0) anyway (its kernel-row-0
+// barrier), so the post puts no new wait in front of the weight-slice loads
 template <bool EXTRA>
 DEV void conv2_core(const bf16* Wg, const bf16* xin, bf16* ws, f32x4 (&acc)[2][2], f32x4& accx, int pg, int cp,
-                    int xsel, int g, int li, int tid, const bf16* s0, int tk = -1) {
+                    int xsel, int g, int li, int tid, const bf16* s0, int tk = -1, unsigned* post = nullptr,
+                    unsigned post_gen = 0u) {
   constexpr int NPX = EXTRA ? 3 : 2;
   const int w = wave_id(), lane = tid & 63, sw = li & 7;
   // Per-lane LDS element offsets, computed once: every fragment read of the loop is then one
@@ -95,7 +100,9 @@ DEV void conv2_core(const bf16* Wg, const bf16* xin, bf16* ws, f32x4 (&acc)[2][2
   accx = zero4();
   if (!s0) ws_dma(Wg, 0, ws, w, lane);
   const bf16* sb0 = s0 ? s0 : ws;
+  if (post) wait_vm_all();                               // (explicit: the barrier below must drain the stores)
   __syncthreads();                                       // (waits vmcnt(0): the DMA has landed)
+  if (post && tid == 0) __hip_atomic_store(post, post_gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // One k-chunk (kw, s) = 2 A + NPX B fragments.  The fragments of chunk j+1 are read into the other
   // register set BEFORE chunk j's MFMAs issue, so the LDS latency of a chunk hides behind the previous
   // chunk's MFMAs (lgkmcnt waits for the older reads only) instead of one exposed latency per chunk.
@@ -140,14 +147,14 @@ DEV void conv2_core(const bf16* Wg, const bf16* xin, bf16* ws, f32x4 (&acc)[2][2
 // is not bound by its LDS read bandwidth; removed in r5.)
 template <class F>
 DEV void conv2_tiles(const bf16* Wg, const bf16* xin, bf16* ws, int w, int g, int li, int tid, const bf16* s0,
-                     F&& fn, int tk = -1) {
+                     F&& fn, int tk = -1, unsigned* post = nullptr, unsigned post_gen = 0u) {
   const int cp = w & 1, pg = w >> 1;
   f32x4 acc[2][2], accx;
   if (w < 4) {
-    conv2_core<true>(Wg, xin, ws, acc, accx, pg, cp, pg, g, li, tid, s0, tk);
+    conv2_core<true>(Wg, xin, ws, acc, accx, pg, cp, pg, g, li, tid, s0, tk, post, post_gen);
     fn(2 * cp + pg, 8, accx);
   } else {
-    conv2_core<false>(Wg, xin, ws, acc, accx, pg, cp, 0, g, li, tid, s0, tk);
+    conv2_core<false>(Wg, xin, ws, acc, accx, pg, cp, 0, g, li, tid, s0, tk, post, post_gen);
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) { fn(2 * cp, pg + 4 * t, acc[0][t]); fn(2 * cp + 1, pg + 4 * t, acc[1][t]); }
@@ -162,9 +169,13 @@ DEV void conv2_tiles(const bf16* Wg, const bf16* xin, bf16* ws, int w, int g, in
 // word) and dp2 is read with sc1 loads (another XCD's L2 may hold a stale copy of those lines).
 constexpr size_t DG_LDS = (C2_XIN + C2_OUT) * 2 + 2304 * 3 + WS_BYTES;
 
+// hand (hand.w set: IN_LAUNCH only, the one-launch backward): dY2 and dP1 are consumed by the
+// weight-gradient roles of the same launch -- word (b, HAND_DY2) is posted from inside the core
+// (conv2_core `post`), word (b, HAND_DP1) after the dP1 stores are drained; the block's LDS is free
+// on return.
 template <bool IN_LAUNCH>
 DEV void conv2_dgrad_image(const DmlcConv2DgradArgs& a, int b, char* smem, Seam seam = Seam{nullptr, 0, 0u},
-                           unsigned* err = nullptr) {
+                           unsigned* err = nullptr, Hand hand = Hand{nullptr, 0u, nullptr}) {
   bf16* dyp = reinterpret_cast<bf16*>(smem);
   bf16* outs = dyp + C2_XIN;
   bf16* dp2 = outs + C2_OUT;                                    // [36][64] staged pool2 grad
@@ -224,7 +235,7 @@ DEV void conv2_dgrad_image(const DmlcConv2DgradArgs& a, int b, char* smem, Seam 
     const int px = 16 * t + li, cb = 16 * ct + 4 * g;
     const bf16x4 v = pack4(acc[0], acc[1], acc[2], acc[3]);
     *reinterpret_cast<bf16x4*>(outs + swz128(px, cb >> 3) + ((cb >> 2) & 1) * 4) = v;
-  });
+  }, -1, hand.w ? hand_word(hand, b, HAND_DY2) : nullptr, hand.gen);
   __syncthreads();
   DMLC_STAMP(DMLC_TK_DGRAD, 3);
   bf16* dp1 = reinterpret_cast<bf16*>(a.dp1) + (size_t)b * 9216;
@@ -233,6 +244,11 @@ DEV void conv2_dgrad_image(const DmlcConv2DgradArgs& a, int b, char* smem, Seam 
     st_out16(dp1, (uint32_t)(p * 64 + c * 8) * 2, __builtin_bit_cast(uint4, lds_b128(outs + swz128(p, c))));
   }
   DMLC_STAMP(DMLC_TK_DGRAD, 4);
+  if (hand.w) {
+    wait_vm_all();
+    __syncthreads();
+    if (tid == 0) hand_post(hand, b, HAND_DP1);
+  }
 }
 
 }  // namespace dmlc

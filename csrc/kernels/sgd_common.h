@@ -257,9 +257,19 @@ DEV void copy_next_row(const DmlcSgdArgs& a, int64_t step, int row, int tid) {
 
 // Publish the step's stats into the ring and bump the device global_step (one wave, lanes < 64).
 // loss / accuracy partials come from the head (an earlier launch).
+// COH: the partials were written (write-through) by head blocks of the SAME launch: sc1 loads.
+template <bool COH = false>
 DEV void publish_step(const DmlcSgdArgs& a, int64_t step, float lr, int lane) {
   float loss = 0.f, corr = 0.f;
-  for (int q = lane; q < a.nhead; q += 64) { loss += a.loss_part[q]; corr += (float)a.correct_part[q]; }
+  for (int q = lane; q < a.nhead; q += 64) {
+    if constexpr (COH) {
+      loss += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(a.loss_part), (uint32_t)q * 4, 0, kSC1));
+      corr += (float)(int)__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(a.correct_part), (uint32_t)q * 4, 0, kSC1);
+    } else {
+      loss += a.loss_part[q];
+      corr += (float)a.correct_part[q];
+    }
+  }
   loss = wave_sum(loss);
   corr = wave_sum(corr);
   if (lane == 0) {

@@ -100,11 +100,14 @@ VARIANT_DEFAULTS = {
     "fc_sgd_in_chain": None,   # single GPU, dW tiles in the fc chain: every fc SGD in their epilogues (default B < 256)
     "grad16": True,            # data parallel, RCCL, bf16 wire, fc chain: the producers write a bf16 flat gradient
                                # (no cast launches around the all-reduce; bitwise the cast path)
+    "bwd_fused": None,         # single GPU, bf16, 128 < B <= 256: fc chain + conv2 dgrad + wgrad/SGD in one launch
 }
 # int32 words of the SGD arrival ticket (DMLC_TICKET_WORDS in csrc/kernels/api.h)
 TICKET_WORDS = 9 * 32
 # int32 words of the wgrad apply-mode barriers (DMLC_WBAR_WORDS); the last line is the error word
 WBAR_WORDS = 20 * 32
+# int32 words of the one-launch backward's per-image hand-off words (DMLC_HAND_WORDS)
+HAND_WORDS = 2 * 256 * 32
 SEG = {M.short(s.name): s for s in M.PARAM_SPECS}
 
 
@@ -421,6 +424,24 @@ class FusedCifarEngine:
         fsc = V["fc_sgd_in_chain"]
         self.fc_sgd_in_chain = (self.fc_fused and self.wgrad_apply and not self.fc_dw_in_wgrad
                                 and (bool(fsc) if fsc is not None else B < 256))
+        # the whole backward -- fc chain, conv2 dgrad, both weight gradients and the SGD -- in ONE launch
+        # (cnn_bwd.hip k_backward): the chain's and the wgrad launch's 256 workgroups are the same 256, so
+        # each block starts its weight-gradient role the moment its own dgrad is done and waits per image
+        # instead of per launch, and the blocks that finish the chain first take the conv2 roles, which
+        # end the step.  Bitwise the two launches (tests/test_bwd_fused_gpu.py).  Where: the chain with
+        # its one-workgroup-per-image dgrad and its dW tiles, the wgrad launch in apply mode on the
+        # full 256-block grid, bf16 state, one rank.  The fc SGD roles of the wgrad launch would read
+        # the chain's flat gradient inside the launch, so this path has the chain apply every fc SGD in
+        # its dW epilogues (fc_sgd_in_chain, also at B = 256) and is off when that variant is forced off.
+        bwf = V["bwd_fused"]
+        bwd_ok = (self.fc_fused and self.fc_dgrad and 128 < B <= 256 and self.dgrad_split == 1
+                  and self.wgrad_apply and not self.fc_dw_in_wgrad and not self.fp8 and world_size == 1
+                  and self.xraw_prefetch and fsc is not False and self.g1 + 4 * self.g2 == 256
+                  and self.g1 % 8 == 0 and self.g2 % 8 == 0)
+        self.bwd_fused = bool(bwd_ok and (bool(bwf) if bwf is not None else True))
+        if self.bwd_fused:
+            self.fc_sgd_in_chain = True
+        self.bwd_hand = torch.zeros(HAND_WORDS if self.bwd_fused else 1, dtype=torch.int32, device=dev)
         self._fc_bwd_sgd = dict(fb, C=[fb["C"][0], p["full_weight_1"]] + fb["C"][2:],
                                 params=fb["params"][:14] + _gemm_params(2304, 384, B, 2304, 0, 384, 0, 384, 4,
                                                                         s_par=FC1_NUMEL)
@@ -554,6 +575,10 @@ class FusedCifarEngine:
             raise RuntimeError("_fc_chain must follow a training _forward")
         if self._dgrad_done:
             raise RuntimeError("the previous fc chain's conv backward never ran")
+        self.ops.fc_chain(*self._fc_chain_args(fused_sgd))
+        self._dgrad_done = self.fc_dgrad
+
+    def _fc_chain_args(self, fused_sgd: bool) -> tuple:
         idx, counter, period = self._fc_src
         self._fc_src = None
         p, gv = self.pv, self.gv
@@ -562,17 +587,31 @@ class FusedCifarEngine:
         if not fused_sgd:
             gv = self.gv_chain                   # (bf16 views on the RCCL bf16 wire)
         g = p if all_sgd else gv                 # every fc SGD here: the master views, else the gradients
-        self.ops.fc_chain(self.p2.view(self.B, 2304), self.fc1n, self.h1part8, p["full_bias_1"], self.fc2t,
-                          p["full_bias_2"], self.fc3t, p["full_bias_3"], self.fc3d, self.labels, idx, counter, period,
-                          1.0 / (self.Bv * self.world_size), self.relu_logits, self.h1, self.h2, self.dl, self.dh1,
-                          self.dh2, self.loss_part, self.correct_part, self.dp2.view(self.B, 2304),
-                          p["full_weight_1"] if fused_sgd else gv["full_weight_1"], g["full_weight_2"],
-                          g["full_weight_3"], g["full_bias_1"], g["full_bias_2"], g["full_bias_3"], fused_sgd,
-                          sched, self.Bv, self.step_t, self.step_sgd, self.fc_sync, self.wbar[10 * 32:10 * 32 + 1],
-                          not (fused_sgd and self.fc_dw_in_wgrad),
-                          *((self.am2, self.w2d, self.dp1, self.dy2) if self.fc_dgrad else (None, None, None, None)),
-                          self.fc2n if all_sgd else None)
-        self._dgrad_done = self.fc_dgrad
+        return (self.p2.view(self.B, 2304), self.fc1n, self.h1part8, p["full_bias_1"], self.fc2t,
+                p["full_bias_2"], self.fc3t, p["full_bias_3"], self.fc3d, self.labels, idx, counter, period,
+                1.0 / (self.Bv * self.world_size), self.relu_logits, self.h1, self.h2, self.dl, self.dh1,
+                self.dh2, self.loss_part, self.correct_part, self.dp2.view(self.B, 2304),
+                p["full_weight_1"] if fused_sgd else gv["full_weight_1"], g["full_weight_2"],
+                g["full_weight_3"], g["full_bias_1"], g["full_bias_2"], g["full_bias_3"], fused_sgd,
+                sched, self.Bv, self.step_t, self.step_sgd, self.fc_sync, self.wbar[10 * 32:10 * 32 + 1],
+                not (fused_sgd and self.fc_dw_in_wgrad),
+                *((self.am2, self.w2d, self.dp1, self.dy2) if self.fc_dgrad else (None, None, None, None)),
+                self.fc2n if all_sgd else None)
+
+    def _backward_fused(self):
+        """The training step's whole backward + SGD as one launch (bwd_fused; cnn_bwd.hip), for the
+        batch of the preceding _forward(train=True)."""
+        if self._fc_src is None:
+            raise RuntimeError("_backward_fused must follow a training _forward")
+        if self._dgrad_done:
+            raise RuntimeError("the previous fc chain's conv backward never ran")
+        fc = self._fc_chain_args(True)
+        # (an op schema holds at most 64 arguments: the first call only stages the wgrad + SGD
+        # arguments on the host, the second launches)
+        self.ops.backward_fused_wgrad(self.data, self.bidx, None, 1, self.cy, self.cx, self.dp1, self.am1,
+                                      self.p1, self.dy2, self.groups2, self.xraw, self.wbar,
+                                      *self._sgd_args(mode=0, fc1_fused=True), fc_acts=None, fc_sgd_done=True)
+        self.ops.backward_fused(self.bwd_hand, *fc)
 
     def _conv_backward(self, src=None, apply: bool = False, reduce: bool = False):
         """apply: + the whole SGD in the wgrad launch (single GPU); reduce: + the conv slab reduction
@@ -647,6 +686,9 @@ class FusedCifarEngine:
             if e & 2:
                 parts.append("k_fc_chain / k_conv12_fwd_split: a hand-off wait timed out; rerun with "
                              "DMLC_FC_FUSED=0 / DMLC_FWD12_SPLIT=0")
+            if e & 4:                      # (generation-valued words: nothing to re-arm)
+                parts.append("k_backward: a per-image dY2 / dP1 hand-off wait timed out; rerun with the engine "
+                             "variant bwd_fused=0")
             if self.fwd12_split:
                 self.c12_flags.zero_()     # a timed-out hand-off can leave a partner's flag raised
             raise RuntimeError("; ".join(parts) + f" (blocks not co-resident, error word {e})")
@@ -790,6 +832,9 @@ class FusedCifarEngine:
         if not self.dp:
             if self.fc1_epilogue:
                 self._forward(self.bidx, None, 1, train=True)
+                if self.bwd_fused:                  # fc chain + dgrad + wgrad + SGD: one launch
+                    self._backward_fused()
+                    return
                 self._fc_backward(fused_sgd=True)
                 if self.wgrad_apply:                # the SGD runs inside the wgrad launch
                     self._conv_backward(apply=True)
