@@ -437,353 +437,341 @@ void head(const Tensor& h1part, const Tensor& b1, const Tensor& w2t, const Tenso
   CHECK_HIP(dmlc_head(&a, stream_of(h1part)));
 }
 
-// the fc chain's arguments (fc_chain and backward_fused take the same list)
-#define DMLC_FC_PARAMS                                                                                    \
-  const Tensor &p2, const Tensor &fc1n, const Tensor &h1part, const Tensor &b1, const Tensor &w2t,          \
-      const Tensor &b2, const Tensor &w3t, const Tensor &b3, const Tensor &w3d, const Tensor &labels,       \
-      const Tensor &idx, const c10::optional<Tensor> &counter, int64_t period, double inv_batch,            \
-      bool relu_logits, const Tensor &h1, const Tensor &h2, const Tensor &dl, const Tensor &dh1,            \
-      const Tensor &dh2, const Tensor &loss_part, const Tensor &correct_part, const Tensor &dp2,            \
-      const Tensor &gw1, const Tensor &gw2, const Tensor &gw3, const Tensor &gb1, const Tensor &gb2,        \
-      const Tensor &gb3, bool fuse_sgd, at::ArrayRef<double> sched, int64_t nvalid, const Tensor &step,     \
-      const c10::optional<Tensor> &step_copy, const Tensor &sync, const Tensor &err, bool dw_tasks,         \
-      const c10::optional<Tensor> &am2, const c10::optional<Tensor> &w2d, const c10::optional<Tensor> &dp1, \
-      const c10::optional<Tensor> &dy2, const c10::optional<Tensor> &fc2n
-#define DMLC_FC_ARGS                                                                                      \
-  p2, fc1n, h1part, b1, w2t, b2, w3t, b3, w3d, labels, idx, counter, period, inv_batch, relu_logits, h1, h2, dl, \
-      dh1, dh2, loss_part, correct_part, dp2, gw1, gw2, gw3, gb1, gb2, gb3, fuse_sgd, sched, nvalid, step,       \
-      step_copy, sync, err, dw_tasks, am2, w2d, dp1, dy2, fc2n
+// ---------------------------------------------------------------------------------------------------
+// The ops below take the engine's device buffers by name: FusedCifarEngine.buf (engine/fused.py), every
+// buffer under its attribute name, a nullable buffer being an absent key.  The dict is passed whole on
+// every call, so the bindings keep no state between calls, and a schema lists only what differs from
+// call to call: the index source, the host order descriptor, off (the flat offsets of the 10 parameter
+// tensors), sched = {lr0, decay, decay_steps, staircase, warmup, grad_scale} and the mode switches.
+// `master` stands first as a plain tensor because the dispatcher finds the backend from plain tensor
+// arguments only.  (A schema cannot mark a dict's tensors as written; these ops write them in place.)
+using Buf = c10::Dict<std::string, Tensor>;
 
-// checks the tensors and fills the chain's arguments; returns whether the conv2 dgrad (g) is on
-static bool make_fc(DMLC_FC_PARAMS, DmlcFcArgs& a, DmlcConv2DgradArgs& g) {
-  const int64_t B = p2.size(0);
-  TORCH_CHECK(B >= 16 && B <= 256 && B % 16 == 0, "fc_chain: batch must be a multiple of 16 in [16, 256]");
-  check(p2, "p2", at::kBFloat16, {B, 2304});
-  check(fc1n, "fc1n", at::kBFloat16, {2, 2304, 384});
-  check(h1part, "h1part", at::kFloat, {8, B, 384});
-  check_numel(b1, "b1", at::kFloat, 384);
-  check(w2t, "w2t", at::kBFloat16, {192, 384});
-  check_numel(b2, "b2", at::kFloat, 192);
-  check(w3t, "w3t", at::kBFloat16, {16, 192});
-  check_numel(b3, "b3", at::kFloat, 10);
-  check(w3d, "w3d", at::kBFloat16, {192, 32});
-  dev(labels, "labels");
-  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.dim() == 1, "labels must be int32 [N]");
-  check(h1, "h1", at::kBFloat16, {B, 384});
-  check(h2, "h2", at::kBFloat16, {B, 192});
-  check(dl, "dl", at::kBFloat16, {B, 16});
-  check(dh1, "dh1", at::kBFloat16, {B, 384});
-  check(dh2, "dh2", at::kBFloat16, {B, 192});
-  check(loss_part, "loss_part", at::kFloat, {B / 4});
-  check(correct_part, "correct_part", at::kInt, {B / 4});
-  check(dp2, "dp2", at::kBFloat16, {B, 2304});
-  // the fc gradients: fp32 views of the flat gradient, or bf16 views (the RCCL bf16 wire, no fused SGD)
-  const bool g16 = gw1.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(!g16 || !fuse_sgd, "fc_chain: bf16 gradient views only without the fused SGD");
-  const auto gt = g16 ? at::kBFloat16 : at::kFloat;
-  check_numel(gw1, "gw1", gt, 2304 * 384);
-  check_numel(gw2, "gw2", gt, 384 * 192);
-  check_numel(gw3, "gw3", gt, 192 * 10);
-  check_numel(gb1, "gb1", gt, 384);
-  check_numel(gb2, "gb2", gt, 192);
-  check_numel(gb3, "gb3", gt, 10);
-  check_numel(step, "step", at::kLong, 1);
-  check_min(sync, "sync", at::kInt, 212 * 32);   // fc_common.h SY_END
-  check_min(err, "err", at::kInt, 1);
-  TORCH_CHECK(sched.size() == 6, "fc_chain: sched = {lr0, decay, decay_steps, staircase, warmup, grad_scale}");
-  if (nvalid < 0) nvalid = B;
-  TORCH_CHECK(nvalid >= 1 && nvalid <= B, "fc_chain: nvalid must be in [1, B]");
-  memset(&a, 0, sizeof(a));
-  a.B = (int)B; a.nvalid = (int)nvalid; a.mtiles = (int)((B + 63) / 64);
-  a.p2 = p2.data_ptr(); a.w1 = fc1n.data_ptr(); a.h1part = h1part.data_ptr<float>();
-  a.b1 = b1.data_ptr<float>(); a.w2t = w2t.data_ptr(); a.b2 = b2.data_ptr<float>();
-  a.w3t = w3t.data_ptr(); a.b3 = b3.data_ptr<float>(); a.w3d = w3d.data_ptr();
-  a.labels = labels.data_ptr<int>(); a.src = index_src(idx, counter, period, B);
-  check_order_fits(a.src, labels.size(0));
-  a.inv_batch = (float)inv_batch; a.relu_logits = relu_logits;
-  a.h1 = h1.data_ptr(); a.h2 = h2.data_ptr(); a.dl = dl.data_ptr(); a.dh1 = dh1.data_ptr(); a.dh2 = dh2.data_ptr();
-  a.loss_part = loss_part.data_ptr<float>(); a.correct_part = correct_part.data_ptr<int>();
-  a.dp2 = dp2.data_ptr();
-  a.gw1 = (float*)gw1.data_ptr(); a.gw2 = (float*)gw2.data_ptr(); a.gw3 = (float*)gw3.data_ptr();
-  a.gb1 = (float*)gb1.data_ptr(); a.gb2 = (float*)gb2.data_ptr(); a.gb3 = (float*)gb3.data_ptr();
-  a.grad_bf16 = g16 ? 1 : 0;
-  a.fuse_sgd = fuse_sgd ? 1 : 0;
-  a.dw_tasks = dw_tasks ? 1 : 0;
-  if (fc2n.has_value()) {
-    // every fc parameter's SGD in the dW tiles' epilogues (fuse_sgd 2, as the wgrad launch runs them):
-    // gw2 / gw3 / gb1..3 are then the fp32 MASTER views and w2t / w3t / w3d + fc2n the bf16 shadows the
-    // epilogues rewrite (the head has read them before the dW tiles' seam)
-    TORCH_CHECK(fuse_sgd && dw_tasks, "fc_chain: the fc SGD in the chain needs fuse_sgd and the dW tiles");
-    check(*fc2n, "fc2n", at::kBFloat16, {384, 192});
-    a.fuse_sgd = 2;
-    a.mw2 = gw2.data_ptr<float>(); a.mw3 = gw3.data_ptr<float>();
-    a.mb1 = gb1.data_ptr<float>(); a.mb2 = gb2.data_ptr<float>(); a.mb3 = gb3.data_ptr<float>();
-    a.fc2n = fc2n->data_ptr(); a.fc2t = w2t.data_ptr(); a.fc3t = w3t.data_ptr(); a.fc3d = w3d.data_ptr();
-  }
-  a.lr0 = (float)sched[0]; a.decay = (float)sched[1]; a.decay_steps = (float)sched[2];
-  a.staircase = sched[3] != 0.0; a.warmup = (float)sched[4]; a.grad_scale = (float)sched[5];
-  a.step = step.data_ptr<int64_t>();
-  a.step_copy = nullptr;
-  if (step_copy.has_value()) {
-    check_numel(*step_copy, "step_copy", at::kLong, 1);
-    a.step_copy = step_copy->data_ptr<int64_t>();
-  }
-  a.sync = reinterpret_cast<unsigned int*>(sync.data_ptr<int>());
-  a.err = reinterpret_cast<unsigned int*>(err.data_ptr<int>());
-  // am2 / w2d / dp1 / dy2: the conv2 input gradient runs in the same launch (one image per workgroup)
-  const bool dg_on = am2.has_value();
-  TORCH_CHECK(dg_on == w2d.has_value() && dg_on == dp1.has_value() && dg_on == dy2.has_value(),
-              "fc_chain: am2, w2d, dp1, dy2 come together");
-  memset(&g, 0, sizeof(g));
-  if (dg_on) {
-    check(*am2, "am2", at::kByte, {B, 6, 6, 64});
-    check(*w2d, "w2d", at::kBFloat16, {64, 1600});
-    check(*dp1, "dp1", at::kBFloat16, {B, 12, 12, 64});
-    check(*dy2, "dy2", at::kBFloat16, {B, 144, 64});
-    g.dp2 = dp2.data_ptr(); g.am2 = am2->data_ptr<uint8_t>(); g.wd = w2d->data_ptr();
-    g.dp1 = dp1->data_ptr(); g.dy2 = dy2->data_ptr(); g.B = (int)B;
-    g.split = B <= 128 ? 1 : 0;          // the chain's 256 workgroups: two per image at B <= 128
-  }
-  return dg_on;
+bool has(const Buf& buf, const char* n) { return buf.contains(n); }
+Tensor need(const Buf& buf, const char* n) {
+  const auto it = buf.find(n);
+  TORCH_CHECK(it != buf.end(), "buf has no '", n, "'");
+  return it->value();
+}
+// the named buffer, checked as check() / check_numel() / check_min() check a tensor
+Tensor need(const Buf& buf, const char* n, at::ScalarType st, std::vector<int64_t> shape) {
+  Tensor t = need(buf, n);
+  check(t, n, st, std::move(shape));
+  return t;
+}
+Tensor need_numel(const Buf& buf, const char* n, at::ScalarType st, int64_t numel) {
+  Tensor t = need(buf, n);
+  check_numel(t, n, st, numel);
+  return t;
+}
+Tensor need_min(const Buf& buf, const char* n, at::ScalarType st, int64_t numel) {
+  Tensor t = need(buf, n);
+  check_min(t, n, st, numel);
+  return t;
 }
 
-// the whole fc chain of a training step, one persistent launch (cnn_fc.hip)
-void fc_chain(DMLC_FC_PARAMS) {
-  DmlcFcArgs a;
-  DmlcConv2DgradArgs g;
-  const bool dg_on = make_fc(DMLC_FC_ARGS, a, g);
-  c10::DeviceGuard guard(p2.device());
-  CHECK_HIP(dmlc_fc_chain(&a, dg_on ? &g : nullptr, stream_of(p2)));
-}
-
-static DmlcSgdArgs make_sgd(const Tensor& master, const Tensor& grad, int64_t mode, double grad_scale, at::IntArrayRef off,
-         const Tensor& part1, const Tensor& partb1, const Tensor& part2, const Tensor& partb2, const Tensor& w1f,
-         const Tensor& w2f, const Tensor& w2d, const Tensor& fc1n, const Tensor& fc2t, const Tensor& fc2n,
-         const Tensor& fc3t, const Tensor& fc3d, const Tensor& step, double lr0, double decay, double decay_steps,
-         bool staircase, const Tensor& ticket, const Tensor& loss_part, const Tensor& correct_part,
-         const Tensor& stats, const c10::optional<Tensor>& w2f8, const c10::optional<Tensor>& amax_w,
-         const c10::optional<Tensor>& scale_w, int64_t roles, bool finalize, int64_t batch,
-         const c10::optional<Tensor>& bidx, const c10::optional<Tensor>& order, double warmup, bool fc1_fused,
-         const c10::optional<Tensor>& step_rd, const c10::optional<Tensor>& xnext,
-         const c10::optional<Tensor>& xdata) {
-  TORCH_CHECK(roles >= 0 && roles <= 2, "sgd roles must be 0..2");
-  TORCH_CHECK(warmup >= 0.0, "sgd: warmup must be >= 0");
-  TORCH_CHECK(mode >= 0 && mode <= 3, "sgd mode must be 0..3");
+// off: returns the end of the last tensor, which master / grad / grad16 must reach
+int64_t check_off(at::IntArrayRef off) {
   TORCH_CHECK(off.size() == 10, "off must have 10 entries");
   static const int64_t numel[10] = {4800, 64, 102400, 64, 884736, 384, 73728, 192, 1920, 10};
   for (int i = 0; i < 10; ++i) {
     TORCH_CHECK(off[i] >= 0 && (i == 0 || off[i] >= off[i - 1] + numel[i - 1]), "bad param offsets");
   }
-  const int64_t end = off[9] + 10;
+  return off[9] + 10;
+}
+
+// the plain `master` argument: long enough, and the dict's own
+float* master_ptr(const Tensor& master, const Buf& buf, int64_t end) {
   check_min(master, "master", at::kFloat, end);
-  // the flat gradient: fp32, or bf16 (DmlcSgdArgs::grad16: the RCCL bf16 wire, modes 1 / 2 only)
-  const bool g16 = grad.scalar_type() == at::kBFloat16;
-  check_min(grad, "grad", g16 ? at::kBFloat16 : at::kFloat, end);
-  TORCH_CHECK(!g16 || mode == 1 || mode == 2, "sgd: a bf16 gradient only in modes 1 / 2 (data parallel)");
+  TORCH_CHECK(need(buf, "master").data_ptr() == master.data_ptr(), "master must be buf['master']");
+  return master.data_ptr<float>();
+}
+
+// Checks the buffers and fills the chain's arguments.  fuse_sgd: the fc1 weights are updated in the dW1
+// epilogue; fc_sgd: so is every other fc parameter (DmlcFcArgs::fuse_sgd 2); dgrad: the conv2 input
+// gradient runs in the launch (g).  Where the chain writes follows from the switches: a segment whose
+// SGD runs here is its view of master, every other one its view of the flat gradient -- grad, or
+// grad16 (bf16 views: the RCCL bf16 wire) where the engine keeps one and no SGD is fused.
+void make_fc(const Tensor& master, const Buf& buf, const Tensor& idx, const c10::optional<Tensor>& counter,
+             int64_t period, at::IntArrayRef off, at::ArrayRef<double> sched, int64_t batch, double inv_batch,
+             bool relu_logits, bool fuse_sgd, bool dw_tasks, bool dgrad, bool fc_sgd, DmlcFcArgs& a,
+             DmlcConv2DgradArgs& g) {
+  const int64_t B = need(buf, "p2").size(0);
+  TORCH_CHECK(B >= 16 && B <= 256 && B % 16 == 0, "fc_chain: batch must be a multiple of 16 in [16, 256]");
+  TORCH_CHECK(sched.size() == 6, "fc_chain: sched = {lr0, decay, decay_steps, staircase, warmup, grad_scale}");
+  TORCH_CHECK(batch >= 1 && batch <= B, "fc_chain: batch (the valid rows) must be in [1, B]");
+  const int64_t end = check_off(off);
+  float* m = master_ptr(master, buf, end);
+  memset(&a, 0, sizeof(a));
+  a.B = (int)B; a.nvalid = (int)batch; a.mtiles = (int)((B + 63) / 64);
+  a.p2 = need(buf, "p2", at::kBFloat16, {B, 6, 6, 64}).data_ptr();        // read as [B][2304]
+  a.w1 = need(buf, "fc1n", at::kBFloat16, {2, 2304, 384}).data_ptr();
+  a.h1part = need(buf, "h1part8", at::kFloat, {8, B, 384}).data_ptr<float>();
+  a.b1 = m + off[5]; a.b2 = m + off[7]; a.b3 = m + off[9];
+  const Tensor fc2t = need(buf, "fc2t", at::kBFloat16, {192, 384});
+  const Tensor fc3t = need(buf, "fc3t", at::kBFloat16, {16, 192});
+  const Tensor fc3d = need(buf, "fc3d", at::kBFloat16, {192, 32});
+  a.w2t = fc2t.data_ptr(); a.w3t = fc3t.data_ptr(); a.w3d = fc3d.data_ptr();
+  const Tensor labels = need(buf, "labels");
+  dev(labels, "labels");
+  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.dim() == 1, "labels must be int32 [N]");
+  a.labels = labels.data_ptr<int>(); a.src = index_src(idx, counter, period, B);
+  check_order_fits(a.src, labels.size(0));
+  a.inv_batch = (float)inv_batch; a.relu_logits = relu_logits;
+  a.h1 = need(buf, "h1", at::kBFloat16, {B, 384}).data_ptr();
+  a.h2 = need(buf, "h2", at::kBFloat16, {B, 192}).data_ptr();
+  a.dl = need(buf, "dl", at::kBFloat16, {B, 16}).data_ptr();
+  a.dh1 = need(buf, "dh1", at::kBFloat16, {B, 384}).data_ptr();
+  a.dh2 = need(buf, "dh2", at::kBFloat16, {B, 192}).data_ptr();
+  a.loss_part = need(buf, "loss_part", at::kFloat, {B / 4}).data_ptr<float>();
+  a.correct_part = need(buf, "correct_part", at::kInt, {B / 4}).data_ptr<int>();
+  a.dp2 = need(buf, "dp2", at::kBFloat16, {B, 6, 6, 64}).data_ptr();      // written as [B][2304]
+  const bool g16 = !fuse_sgd && has(buf, "grad16");
+  char* mb = reinterpret_cast<char*>(m);
+  char* gb = static_cast<char*>(g16 ? need_min(buf, "grad16", at::kBFloat16, end).data_ptr()
+                                    : need_min(buf, "grad", at::kFloat, end).data_ptr());
+  auto seg = [&](int i, bool in_master) {
+    return reinterpret_cast<float*>(in_master ? mb + 4 * off[i] : gb + (g16 ? 2 : 4) * off[i]);
+  };
+  a.gw1 = seg(4, fuse_sgd); a.gw2 = seg(6, fc_sgd); a.gw3 = seg(8, fc_sgd);
+  a.gb1 = seg(5, fc_sgd); a.gb2 = seg(7, fc_sgd); a.gb3 = seg(9, fc_sgd);
+  a.grad_bf16 = g16 ? 1 : 0;
+  a.fuse_sgd = fuse_sgd ? 1 : 0;
+  a.dw_tasks = dw_tasks ? 1 : 0;
+  if (fc_sgd) {
+    // every fc parameter's SGD in the dW tiles' epilogues (fuse_sgd 2, as the wgrad launch runs them):
+    // gw2 / gw3 / gb1..3 are then the fp32 MASTER views and w2t / w3t / w3d + fc2n the bf16 shadows the
+    // epilogues rewrite (the head has read them before the dW tiles' seam)
+    TORCH_CHECK(fuse_sgd && dw_tasks, "fc_chain: the fc SGD in the chain needs fuse_sgd and the dW tiles");
+    a.fuse_sgd = 2;
+    a.mw2 = a.gw2; a.mw3 = a.gw3; a.mb1 = a.gb1; a.mb2 = a.gb2; a.mb3 = a.gb3;
+    a.fc2n = need(buf, "fc2n", at::kBFloat16, {384, 192}).data_ptr();
+    a.fc2t = fc2t.data_ptr(); a.fc3t = fc3t.data_ptr(); a.fc3d = fc3d.data_ptr();
+  }
+  a.lr0 = (float)sched[0]; a.decay = (float)sched[1]; a.decay_steps = (float)sched[2];
+  a.staircase = sched[3] != 0.0; a.warmup = (float)sched[4]; a.grad_scale = (float)sched[5];
+  a.step = need_numel(buf, "step_t", at::kLong, 1).data_ptr<int64_t>();
+  a.step_copy = need_numel(buf, "step_sgd", at::kLong, 1).data_ptr<int64_t>();
+  a.sync = reinterpret_cast<unsigned int*>(need_min(buf, "fc_sync", at::kInt, 212 * 32).data_ptr<int>());   // fc_common.h SY_END
+  // the sticky error word is the wgrad barriers' (wbar[10 * 32])
+  a.err = reinterpret_cast<unsigned int*>(need_numel(buf, "wbar", at::kInt, DMLC_WBAR_WORDS).data_ptr<int>()) + 10 * 32;
+  memset(&g, 0, sizeof(g));
+  if (dgrad) {
+    // one image per workgroup; am2 / w2d / dp1 / dy2 come together (need() names a missing one)
+    g.dp2 = a.dp2; g.am2 = need(buf, "am2", at::kByte, {B, 6, 6, 64}).data_ptr<uint8_t>();
+    g.wd = need(buf, "w2d", at::kBFloat16, {64, 1600}).data_ptr();
+    g.dp1 = need(buf, "dp1", at::kBFloat16, {B, 12, 12, 64}).data_ptr();
+    g.dy2 = need(buf, "dy2", at::kBFloat16, {B, 144, 64}).data_ptr(); g.B = (int)B;
+    g.split = B <= 128 ? 1 : 0;          // the chain's 256 workgroups: two per image at B <= 128
+  }
+}
+
+// the whole fc chain of a training step, one persistent launch (cnn_fc.hip)
+void fc_chain(const Tensor& master, const Buf& buf, const Tensor& idx, const c10::optional<Tensor>& counter,
+              int64_t period, at::IntArrayRef off, at::ArrayRef<double> sched, int64_t batch, double inv_batch,
+              bool relu_logits, bool fuse_sgd, bool dw_tasks, bool dgrad, bool fc_sgd) {
+  DmlcFcArgs a;
+  DmlcConv2DgradArgs g;
+  make_fc(master, buf, idx, counter, period, off, sched, batch, inv_batch, relu_logits, fuse_sgd, dw_tasks, dgrad,
+          fc_sgd, a, g);
+  c10::DeviceGuard guard(master.device());
+  CHECK_HIP(dmlc_fc_chain(&a, dgrad ? &g : nullptr, stream_of(master)));
+}
+
+// prefetch: the finalizing launch also gathers the next step's raw images into xraw (needs data, bidx)
+DmlcSgdArgs make_sgd(const Tensor& master, const Buf& buf, at::IntArrayRef off, at::ArrayRef<double> sched,
+                     const c10::optional<Tensor>& order, int64_t mode, int64_t roles, bool finalize, bool fc1_fused,
+                     int64_t batch, bool prefetch) {
+  TORCH_CHECK(roles >= 0 && roles <= 2, "sgd roles must be 0..2");
+  TORCH_CHECK(sched.size() == 6, "sgd: sched = {lr0, decay, decay_steps, staircase, warmup, grad_scale}");
+  TORCH_CHECK(sched[4] >= 0.0, "sgd: warmup must be >= 0");
+  TORCH_CHECK(mode >= 0 && mode <= 3, "sgd mode must be 0..3");
+  const int64_t end = check_off(off);
+  DmlcSgdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.master = master_ptr(master, buf, end);
+  // the flat gradient: fp32, or in modes 1 / 2 (data parallel) the bf16 one where the engine keeps it
+  // (DmlcSgdArgs::grad16: the RCCL bf16 wire)
+  if (has(buf, "grad16") && (mode == 1 || mode == 2)) a.grad16 = need_min(buf, "grad16", at::kBFloat16, end).data_ptr();
+  else a.grad = need_min(buf, "grad", at::kFloat, end).data_ptr<float>();
+  const Tensor part1 = need(buf, "part1"), part2 = need(buf, "part2");
   const int64_t g1 = part1.size(0), g2 = part2.size(0);
   check(part1, "part1", at::kFloat, {g1, 80, 64});
-  check(partb1, "partb1", at::kFloat, {g1, 64});
   check(part2, "part2", at::kFloat, {g2, 1600, 64});
-  check(partb2, "partb2", at::kFloat, {g2, 64});
+  a.part1 = part1.data_ptr<float>(); a.g1 = (int)g1;
+  a.partb1 = need(buf, "partb1", at::kFloat, {g1, 64}).data_ptr<float>();
+  a.part2 = part2.data_ptr(); a.g2 = (int)g2;
+  a.partb2 = need(buf, "partb2", at::kFloat, {g2, 64}).data_ptr<float>();
+  const Tensor loss_part = need(buf, "loss_part"), correct_part = need(buf, "correct_part");
   TORCH_CHECK(loss_part.numel() >= 1, "loss partials missing");
-  const int64_t B = batch;
-  TORCH_CHECK(B >= 1 && B <= 4 * loss_part.numel(), "sgd: batch (valid rows) exceeds the head's rows");
-  check(w1f, "w1f", at::kBFloat16, {64, 96});
-  check(w2f, "w2f", at::kBFloat16, {64, 1600});
-  check(w2d, "w2d", at::kBFloat16, {64, 1600});
-  check(fc1n, "fc1n", at::kBFloat16, {2, 2304, 384});          // step-parity double buffer
+  TORCH_CHECK(batch >= 1 && batch <= 4 * loss_part.numel(), "sgd: batch (valid rows) exceeds the head's rows");
+  a.B = (int)batch;
+  a.mode = (int)mode; a.grad_scale = (float)sched[5];
+  for (int i = 0; i < 10; ++i) a.off[i] = (int)off[i];
+  a.w1f = need(buf, "w1f", at::kBFloat16, {64, 96}).data_ptr();
+  a.w2f = need(buf, "w2f", at::kBFloat16, {64, 1600}).data_ptr();
+  a.w2d = need(buf, "w2d", at::kBFloat16, {64, 1600}).data_ptr();
+  a.fc1n = need(buf, "fc1n", at::kBFloat16, {2, 2304, 384}).data_ptr();          // step-parity double buffer
   TORCH_CHECK(!fc1_fused || mode == 0, "sgd: fc1_fused only in mode 0 (single GPU)");
-  check(fc2t, "fc2t", at::kBFloat16, {192, 384});
-  check(fc2n, "fc2n", at::kBFloat16, {384, 192});
-  check(fc3t, "fc3t", at::kBFloat16, {16, 192});
-  check(fc3d, "fc3d", at::kBFloat16, {192, 32});
-  check_numel(step, "step", at::kLong, 1);
-  check_numel(ticket, "ticket", at::kInt, DMLC_TICKET_WORDS);
+  a.fc2t = need(buf, "fc2t", at::kBFloat16, {192, 384}).data_ptr();
+  a.fc2n = need(buf, "fc2n", at::kBFloat16, {384, 192}).data_ptr();
+  a.fc3t = need(buf, "fc3t", at::kBFloat16, {16, 192}).data_ptr();
+  a.fc3d = need(buf, "fc3d", at::kBFloat16, {192, 32}).data_ptr();
+  const Tensor step = need_numel(buf, "step_t", at::kLong, 1);
+  a.step = step.data_ptr<int64_t>();
+  // the step the launch reads: the head's copy (step_sgd), so one workgroup can bump step_t without a
+  // ticket; the shadow refresh (mode 3) follows no head and reads step_t itself
+  a.step_rd = mode == 3 ? a.step : need_numel(buf, "step_sgd", at::kLong, 1).data_ptr<int64_t>();
+  a.lr0 = (float)sched[0]; a.decay = (float)sched[1]; a.decay_steps = (float)sched[2];
+  a.staircase = sched[3] != 0.0; a.warmup = (float)sched[4]; a.fc1_fused = fc1_fused ? 1 : 0;
+  a.ticket = reinterpret_cast<unsigned int*>(need_numel(buf, "ticket", at::kInt, DMLC_TICKET_WORDS).data_ptr<int>());
   dev(loss_part, "loss_part"); dev(correct_part, "correct_part");
   TORCH_CHECK(loss_part.scalar_type() == at::kFloat && correct_part.scalar_type() == at::kInt &&
                   loss_part.numel() == correct_part.numel(), "loss/correct partials mismatch");
-  dev(stats, "stats");
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.dim() == 2 && stats.size(1) == 4, "stats must be [R,4] fp32");
-  DmlcSgdArgs a;
-  a.master = master.data_ptr<float>();
-  a.grad = g16 ? nullptr : grad.data_ptr<float>();
-  a.grad16 = g16 ? grad.data_ptr() : nullptr;
-  a.mode = (int)mode; a.grad_scale = (float)grad_scale;
-  for (int i = 0; i < 10; ++i) a.off[i] = (int)off[i];
-  a.part1 = part1.data_ptr<float>(); a.partb1 = partb1.data_ptr<float>(); a.g1 = (int)g1;
-  a.part2 = part2.data_ptr(); a.g2 = (int)g2;
-  a.partb2 = partb2.data_ptr<float>(); a.B = (int)B;
-  a.w1f = w1f.data_ptr(); a.w2f = w2f.data_ptr(); a.w2d = w2d.data_ptr(); a.fc1n = fc1n.data_ptr();
-  a.fc2t = fc2t.data_ptr(); a.fc2n = fc2n.data_ptr(); a.fc3t = fc3t.data_ptr(); a.fc3d = fc3d.data_ptr();
-  a.step = step.data_ptr<int64_t>(); a.lr0 = (float)lr0;
-  a.step_rd = a.step;
-  if (step_rd.has_value()) {
-    check_numel(*step_rd, "step_rd", at::kLong, 1);
-    a.step_rd = step_rd->data_ptr<int64_t>();
-  } a.decay = (float)decay;
-  a.decay_steps = (float)decay_steps; a.staircase = staircase; a.warmup = (float)warmup; a.fc1_fused = fc1_fused ? 1 : 0;
-  a.ticket = reinterpret_cast<unsigned int*>(ticket.data_ptr<int>());
   a.loss_part = loss_part.data_ptr<float>(); a.correct_part = correct_part.data_ptr<int>();
   a.nhead = (int)loss_part.numel();
+  const Tensor stats = need(buf, "stats");
+  dev(stats, "stats");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.dim() == 2 && stats.size(1) == 4, "stats must be [R,4] fp32");
   a.stats = stats.data_ptr<float>(); a.stats_len = (int)stats.size(0);
-  a.w2f8 = nullptr; a.w2d8 = nullptr; a.amax_w = nullptr; a.scale_w = nullptr;
   a.roles = (int)roles; a.finalize = finalize ? 1 : 0;
-  if (w2f8.has_value()) {
-    TORCH_CHECK(amax_w.has_value() && scale_w.has_value(), "fp8 shadow needs amax_w and scale_w");
+  if (has(buf, "w2f8")) {                  // the fp8 shadow needs amax_w and scale_w (need() names a missing one)
+    const Tensor w2f8 = need(buf, "w2f8");
     // [64][1600] = the forward shadow only; [2][64][1600] = forward + the fp8 dgrad's flipped copy
-    if (w2f8->dim() == 3) check(*w2f8, "w2f8", at::kByte, {2, 64, 1600});
-    else check(*w2f8, "w2f8", at::kByte, {64, 1600});
-    check_numel(*amax_w, "amax_w", at::kFloat, 2 * 400);   // [2 slots][400 conv2-row blocks]
-    check_numel(*scale_w, "scale_w", at::kFloat, 2);
-    a.w2f8 = w2f8->data_ptr<uint8_t>(); a.amax_w = amax_w->data_ptr<float>(); a.scale_w = scale_w->data_ptr<float>();
-    if (w2f8->dim() == 3) a.w2d8 = a.w2f8 + 64 * 1600;
+    if (w2f8.dim() == 3) check(w2f8, "w2f8", at::kByte, {2, 64, 1600});
+    else check(w2f8, "w2f8", at::kByte, {64, 1600});
+    a.w2f8 = w2f8.data_ptr<uint8_t>();
+    a.amax_w = need_numel(buf, "amax_w", at::kFloat, 2 * 400).data_ptr<float>();   // [2 slots][400 conv2-row blocks]
+    a.scale_w = need_numel(buf, "scale_w", at::kFloat, 2).data_ptr<float>();
+    if (w2f8.dim() == 3) a.w2d8 = a.w2f8 + 64 * 1600;
   }
-  a.bidx = nullptr; a.bidx_n = 0;
-  memset(&a.next, 0, sizeof(a.next));
-  if (bidx.has_value()) {
+  if (has(buf, "bidx")) {
+    const Tensor bidx = need(buf, "bidx");
     TORCH_CHECK(order.has_value(), "sgd: bidx needs the order descriptor");
-    dev(*bidx, "bidx");
-    TORCH_CHECK(bidx->scalar_type() == at::kInt && bidx->dim() == 1 && bidx->numel() >= 1 &&
-                    bidx->numel() <= 4096, "bidx must be int32 [Bpad <= 4096]");
+    dev(bidx, "bidx");
+    TORCH_CHECK(bidx.scalar_type() == at::kInt && bidx.dim() == 1 && bidx.numel() >= 1 &&
+                    bidx.numel() <= 4096, "bidx must be int32 [Bpad <= 4096]");
     TORCH_CHECK(!order->is_cuda() && order->scalar_type() == at::kLong && order->numel() == 6,
                 "sgd: order must be the host int64 [6] descriptor");
     const int64_t* d = order->data_ptr<int64_t>();
     TORCH_CHECK(d[2] >= 1 && d[4] >= 1, "sgd: bad order descriptor");
-    a.next = index_src(*order, step, d[0] / (d[2] * d[4]), bidx->numel());   // validates it
+    a.next = index_src(*order, step, d[0] / (d[2] * d[4]), bidx.numel());   // validates it
     TORCH_CHECK(a.next.idx_base == nullptr, "sgd: order must be the host descriptor");
-    a.bidx = bidx->data_ptr<int>(); a.bidx_n = (int)bidx->numel();
+    a.bidx = bidx.data_ptr<int>(); a.bidx_n = (int)bidx.numel();
   }
-  a.xnext = nullptr; a.xdata = nullptr;
-  if (xnext.has_value()) {
-    TORCH_CHECK(xdata.has_value() && a.bidx, "sgd: xnext needs the dataset and bidx");
-    check(*xnext, "xnext", at::kByte, {a.bidx_n, 3072});
-    check_data(*xdata);
-    TORCH_CHECK(a.next.n <= xdata->size(0), "sgd: the order's rows exceed the dataset");
-    a.xnext = xnext->data_ptr<uint8_t>(); a.xdata = xdata->data_ptr<uint8_t>();
+  if (prefetch) {
+    TORCH_CHECK(a.bidx, "sgd: prefetching the next images needs the dataset and bidx");
+    const Tensor xdata = need(buf, "data");
+    check_data(xdata);
+    TORCH_CHECK(a.next.n <= xdata.size(0), "sgd: the order's rows exceed the dataset");
+    a.xnext = need(buf, "xraw", at::kByte, {a.bidx_n, 3072}).data_ptr<uint8_t>(); a.xdata = xdata.data_ptr<uint8_t>();
   }
   return a;
 }
 
-#define DMLC_SGD_PARAMS                                                                                  \
-  const Tensor &master, const Tensor &grad, int64_t mode, double grad_scale, at::IntArrayRef off,          \
-      const Tensor &part1, const Tensor &partb1, const Tensor &part2, const Tensor &partb2, const Tensor &w1f, \
-      const Tensor &w2f, const Tensor &w2d, const Tensor &fc1n, const Tensor &fc2t, const Tensor &fc2n,     \
-      const Tensor &fc3t, const Tensor &fc3d, const Tensor &step, double lr0, double decay, double decay_steps, \
-      bool staircase, const Tensor &ticket, const Tensor &loss_part, const Tensor &correct_part,            \
-      const Tensor &stats, const c10::optional<Tensor> &w2f8, const c10::optional<Tensor> &amax_w,          \
-      const c10::optional<Tensor> &scale_w, int64_t roles, bool finalize, int64_t batch,                    \
-      const c10::optional<Tensor> &bidx, const c10::optional<Tensor> &order, double warmup, bool fc1_fused,  \
-      const c10::optional<Tensor> &step_rd, const c10::optional<Tensor> &xnext, const c10::optional<Tensor> &xdata
-#define DMLC_SGD_ARGS                                                                                     \
-  master, grad, mode, grad_scale, off, part1, partb1, part2, partb2, w1f, w2f, w2d, fc1n, fc2t, fc2n, fc3t, fc3d, \
-      step, lr0, decay, decay_steps, staircase, ticket, loss_part, correct_part, stats, w2f8, amax_w, scale_w,  \
-      roles, finalize, batch, bidx, order, warmup, fc1_fused, step_rd, xnext, xdata
+void sgd(const Tensor& master, const Buf& buf, at::IntArrayRef off, at::ArrayRef<double> sched,
+         const c10::optional<Tensor>& order, int64_t mode, int64_t roles, bool finalize, bool fc1_fused, int64_t batch,
+         bool prefetch) {
+  DmlcSgdArgs a = make_sgd(master, buf, off, sched, order, mode, roles, finalize, fc1_fused, batch, prefetch);
+  c10::DeviceGuard guard(master.device());
+  CHECK_HIP(dmlc_sgd(&a, stream_of(master)));
+}
 
 // data parallel: the xGMI exchange of the whole flat gradient with the SGD update in its epilogue
-// (xgmi_allreduce.hip); `grad` must be the xGMI context's buffer
-void xgmi_allreduce_sgd(int64_t ctx, int64_t blocks, bool bf16_wire, DMLC_SGD_PARAMS) {
+// (xgmi_allreduce.hip): apply mode (2) over every role, bf16 shadows, the head's step copy;
+// buf['grad'] must be the xGMI context's buffer
+void xgmi_allreduce_sgd(int64_t ctx, int64_t blocks, bool bf16_wire, const Tensor& master, const Buf& buf,
+                        at::IntArrayRef off, at::ArrayRef<double> sched, const c10::optional<Tensor>& order,
+                        int64_t batch, bool prefetch) {
   TORCH_CHECK(blocks >= 0 && blocks <= DMLC_XGMI_MAX_BLOCKS, "xgmi_allreduce_sgd: blocks must be in [0,512]");
-  TORCH_CHECK(mode == 2 && roles == 0 && finalize && !fc1_fused && !w2f8.has_value() && step_rd.has_value(),
-              "xgmi_allreduce_sgd: apply mode (2) over every role, bf16 shadows, the head's step copy");
-  DmlcSgdArgs a = make_sgd(DMLC_SGD_ARGS);
+  DmlcSgdArgs a = make_sgd(master, buf, off, sched, order, 2, 0, true, false, batch, prefetch);
+  TORCH_CHECK(!a.w2f8, "xgmi_allreduce_sgd: bf16 shadows only");
   TORCH_CHECK(!a.grad16, "xgmi_allreduce_sgd: the exchange buffer is fp32");
   c10::DeviceGuard guard(master.device());
   CHECK_HIP(dmlc_xgmi_allreduce_sgd((int)ctx, (int)blocks, bf16_wire ? 1 : 0, &a, stream_of(master)));
 }
 
-void sgd(DMLC_SGD_PARAMS) {
-  DmlcSgdArgs a = make_sgd(DMLC_SGD_ARGS);
-  c10::DeviceGuard guard(master.device());
-  CHECK_HIP(dmlc_sgd(&a, stream_of(master)));
-}
-
-// Single GPU: the weight gradients AND the whole SGD step in one launch (cnn_wgrad.hip apply mode).
-// The wgrad arguments come first (data .. xraw), then the barrier words, then sgd()'s arguments
-// (whose slab tensors must be the wgrad's).
-#define DMLC_WGRAD_SGD_PARAMS                                                                              \
-  const Tensor &data, const Tensor &idx, const c10::optional<Tensor> &counter, int64_t period, int64_t cy,   \
-      int64_t cx, const Tensor &dp1, const Tensor &am1, const Tensor &p1, const Tensor &dy2,                 \
-      int64_t groups2, const Tensor &xraw, const Tensor &bar, DMLC_SGD_PARAMS,                               \
-      const c10::optional<at::TensorList> fc_acts, bool fc_sgd_done, const c10::optional<at::TensorList> fp8
-#define DMLC_WGRAD_SGD_ARGS                                                                                \
-  data, idx, counter, period, cy, cx, dp1, am1, p1, dy2, groups2, xraw, bar, DMLC_SGD_ARGS, fc_acts, fc_sgd_done, fp8
-
-static DmlcWgradArgs make_wgrad_sgd(DMLC_WGRAD_SGD_PARAMS) {
-  DmlcWgradArgs a = make_wgrad(data, idx, counter, period, cy, cx, dp1, am1, part1, partb1, p1, dy2, part2, partb2,
-                               groups2, xraw, fp8);
-  TORCH_CHECK((mode == 0 && fc1_fused && step_rd.has_value() && roles == 0 && finalize &&
-               grad_scale == 1.0) || (mode == 1 && roles == 0),
-              "wgrad_sgd: the single-GPU mode-0 step (fc1 epilogue, the head's step copy) or mode 1 (reduce only)");
-  check_numel(bar, "bar", at::kInt, DMLC_WBAR_WORDS);
-  a.sgd = make_sgd(DMLC_SGD_ARGS);
+// The weight gradients AND the SGD in one launch (cnn_wgrad.hip apply mode): mode 0 = the whole
+// single-GPU step (the fc1 update ran in the dW1 epilogue, the step read from the head's copy), mode 1
+// = the conv slab reduction into the flat gradient only.  fc_dw: the fc weight-gradient tiles and every
+// fc SGD run in this launch too; fc_sgd_done: the fc chain applied every fc SGD.
+DmlcWgradArgs make_wgrad_sgd(const Tensor& master, const Buf& buf, const Tensor& idx,
+                             const c10::optional<Tensor>& counter, int64_t period, at::IntArrayRef off,
+                             at::ArrayRef<double> sched, const c10::optional<Tensor>& order, int64_t mode,
+                             int64_t cy, int64_t cx, int64_t groups2, int64_t batch, bool prefetch, bool fc_dw,
+                             bool fc_sgd_done) {
+  TORCH_CHECK(mode == 0 || mode == 1, "wgrad_sgd: mode 0 (the single-GPU step) or mode 1 (reduce only)");
+  // the fp8 conv2 weight gradient's operands come together
+  c10::optional<std::vector<Tensor>> fp8;
+  if (has(buf, "p1f8")) fp8 = std::vector<Tensor>{need(buf, "p1f8"), need(buf, "dy2f8"), need(buf, "sx8"), need(buf, "sy_img")};
+  DmlcWgradArgs a = make_wgrad(need(buf, "data"), idx, counter, period, cy, cx, need(buf, "dp1"), need(buf, "am1"),
+                               need(buf, "part1"), need(buf, "partb1"), need(buf, "p1"), need(buf, "dy2"),
+                               need(buf, "part2"), need(buf, "partb2"), groups2, need(buf, "xraw"),
+                               fp8 ? c10::optional<at::TensorList>(*fp8) : c10::nullopt);
+  a.sgd = make_sgd(master, buf, off, sched, order, mode, 0, true, mode == 0, batch, prefetch);
+  TORCH_CHECK(mode != 0 || sched[5] == 1.0, "wgrad_sgd: the single-GPU step takes no gradient scale");
   a.apply = 1;
-  a.bar = reinterpret_cast<unsigned int*>(bar.data_ptr<int>());
+  a.bar = reinterpret_cast<unsigned int*>(need_numel(buf, "wbar", at::kInt, DMLC_WBAR_WORDS).data_ptr<int>());
   // conv1 blocks help reduce the conv2 slabs unless they also carry the fc dW tiles at B <= 128 (then
   // they arrive too late: 65.8 vs 67.2 us at B=128 without helpers, profiles/r5_wgrad_helpers_ab.txt;
   // with helpers 75.0 vs 75.7 at B=256)
-  a.helpers = (a.w1.B > 128 || !fc_acts.has_value()) ? 1 : 0;
+  a.helpers = (a.w1.B > 128 || !fc_dw) ? 1 : 0;
   a.fc_in_launch = 0;
   a.fc_done = fc_sgd_done ? 1 : 0;             // the fc chain applied every fc SGD: no fc roles here
-  TORCH_CHECK(!fc_sgd_done || (mode == 0 && !fc_acts.has_value()), "wgrad_sgd: fc_sgd_done is the chain's mode-0 step");
+  TORCH_CHECK(!fc_sgd_done || (mode == 0 && !fc_dw), "wgrad_sgd: fc_sgd_done is the chain's mode-0 step");
   memset(&a.fc, 0, sizeof(a.fc));
-  if (fc_acts.has_value()) {
-    // the fc weight-gradient tiles + every fc SGD run in this launch (fc_common.h): fc_acts = the fc
-    // chain's activations {p2 [B][2304], h1, h2, dl, dh1, dh2}; masters / shadows from the SGD args
-    const at::TensorList t = *fc_acts;
-    TORCH_CHECK(t.size() == 6 && mode == 0 && fc1_fused, "wgrad_sgd: fc_acts = {p2, h1, h2, dl, dh1, dh2} in mode 0");
-    const int64_t B = t[0].size(0);
+  if (fc_dw) {
+    // the fc weight-gradient tiles + every fc SGD run in this launch (fc_common.h), on the fc chain's
+    // activations p2 (read as [B][2304]), h1, h2, dl, dh1, dh2; masters / shadows as the SGD's
+    TORCH_CHECK(mode == 0, "wgrad_sgd: the fc tiles run in mode 0");
+    const int64_t B = need(buf, "p2").size(0);
     TORCH_CHECK(B >= 16 && B <= 256 && B % 16 == 0, "wgrad_sgd: fc tiles need a batch in [16, 256]");
-    check(t[0], "p2", at::kBFloat16, {B, 2304});
-    check(t[1], "h1", at::kBFloat16, {B, 384});
-    check(t[2], "h2", at::kBFloat16, {B, 192});
-    check(t[3], "dl", at::kBFloat16, {B, 16});
-    check(t[4], "dh1", at::kBFloat16, {B, 384});
-    check(t[5], "dh2", at::kBFloat16, {B, 192});
-    check(fc2n, "fc2n", at::kBFloat16, {384, 192});
-    check(fc2t, "fc2t", at::kBFloat16, {192, 384});
     DmlcFcArgs& f = a.fc;
     f.B = (int)B; f.nvalid = (int)B; f.mtiles = (int)((B + 63) / 64);
-    f.p2 = t[0].data_ptr(); f.w1 = fc1n.data_ptr();
-    f.h1 = t[1].data_ptr(); f.h2 = t[2].data_ptr(); f.dl = t[3].data_ptr(); f.dh1 = t[4].data_ptr();
-    f.dh2 = t[5].data_ptr();
-    float* m = master.data_ptr<float>();
+    f.p2 = need(buf, "p2", at::kBFloat16, {B, 6, 6, 64}).data_ptr(); f.w1 = a.sgd.fc1n;
+    f.h1 = need(buf, "h1", at::kBFloat16, {B, 384}).data_ptr();
+    f.h2 = need(buf, "h2", at::kBFloat16, {B, 192}).data_ptr();
+    f.dl = need(buf, "dl", at::kBFloat16, {B, 16}).data_ptr();
+    f.dh1 = need(buf, "dh1", at::kBFloat16, {B, 384}).data_ptr();
+    f.dh2 = need(buf, "dh2", at::kBFloat16, {B, 192}).data_ptr();
+    float* m = a.sgd.master;
     f.gw1 = m + off[4]; f.mb1 = m + off[5]; f.mw2 = m + off[6]; f.mb2 = m + off[7]; f.mw3 = m + off[8];
     f.mb3 = m + off[9];
-    f.fc2n = fc2n.data_ptr(); f.fc2t = fc2t.data_ptr(); f.fc3t = fc3t.data_ptr(); f.fc3d = fc3d.data_ptr();
+    f.fc2n = a.sgd.fc2n; f.fc2t = a.sgd.fc2t; f.fc3t = a.sgd.fc3t; f.fc3d = a.sgd.fc3d;
     f.fuse_sgd = 2; f.dw_tasks = 1;
-    f.lr0 = (float)lr0; f.decay = (float)decay; f.decay_steps = (float)decay_steps; f.staircase = staircase;
-    f.warmup = (float)warmup; f.grad_scale = (float)grad_scale;
+    f.lr0 = a.sgd.lr0; f.decay = a.sgd.decay; f.decay_steps = a.sgd.decay_steps; f.staircase = a.sgd.staircase;
+    f.warmup = a.sgd.warmup; f.grad_scale = a.sgd.grad_scale;
     f.err = a.bar + 10 * 32;
     a.fc_in_launch = 1;
   }
   return a;
 }
 
-void wgrad_sgd(DMLC_WGRAD_SGD_PARAMS) {
-  const DmlcWgradArgs a = make_wgrad_sgd(DMLC_WGRAD_SGD_ARGS);
-  c10::DeviceGuard guard(dp1.device());
-  CHECK_HIP(dmlc_wgrad(&a, stream_of(dp1)));
+void wgrad_sgd(const Tensor& master, const Buf& buf, const Tensor& idx, const c10::optional<Tensor>& counter,
+               int64_t period, at::IntArrayRef off, at::ArrayRef<double> sched, const c10::optional<Tensor>& order,
+               int64_t mode, int64_t cy, int64_t cx, int64_t groups2, int64_t batch, bool prefetch, bool fc_dw,
+               bool fc_sgd_done) {
+  const DmlcWgradArgs a = make_wgrad_sgd(master, buf, idx, counter, period, off, sched, order, mode, cy, cx, groups2,
+                                         batch, prefetch, fc_dw, fc_sgd_done);
+  c10::DeviceGuard guard(master.device());
+  CHECK_HIP(dmlc_wgrad(&a, stream_of(master)));
 }
 
-// The whole backward in one launch (cnn_bwd.hip).  A schema takes at most 64 arguments, so the launch
-// is described by two calls: backward_fused_wgrad stages wgrad_sgd's arguments (host side only, no
-// launch), backward_fused adds fc_chain's and launches once.
-static thread_local DmlcWgradArgs staged_wgrad;
-static thread_local bool staged_wgrad_set = false;
-void backward_fused_wgrad(DMLC_WGRAD_SGD_PARAMS) {
-  staged_wgrad = make_wgrad_sgd(DMLC_WGRAD_SGD_ARGS);
-  staged_wgrad_set = true;
-}
-void backward_fused(const Tensor& hand, DMLC_FC_PARAMS) {
-  TORCH_CHECK(staged_wgrad_set, "backward_fused: backward_fused_wgrad must come first");
-  staged_wgrad_set = false;
-  check_numel(hand, "hand", at::kInt, DMLC_HAND_WORDS);
+// The whole backward in one launch (cnn_bwd.hip): the fc chain with the fc1 and every other fc SGD in
+// its dW epilogues and the conv2 dgrad behind it, then wgrad_sgd's mode-0 step with the next images
+// prefetched -- the one configuration the launch exists in (its launcher checks the rest), on one
+// index source: the chain's labels and the weight gradient's images are the same batch rows.
+void backward_fused(const Tensor& master, const Buf& buf, const Tensor& idx, const c10::optional<Tensor>& counter,
+                    int64_t period, at::IntArrayRef off, at::ArrayRef<double> sched, const c10::optional<Tensor>& order,
+                    int64_t cy, int64_t cx, int64_t groups2, int64_t batch, double inv_batch, bool relu_logits) {
   DmlcFcArgs a;
   DmlcConv2DgradArgs g;
-  const bool dg_on = make_fc(DMLC_FC_ARGS, a, g);
-  TORCH_CHECK(dg_on, "backward_fused: the conv2 dgrad (am2, w2d, dp1, dy2) runs in the launch");
-  c10::DeviceGuard guard(p2.device());
-  CHECK_HIP(dmlc_backward(&a, &g, &staged_wgrad, reinterpret_cast<unsigned int*>(hand.data_ptr<int>()), stream_of(p2)));
+  make_fc(master, buf, idx, counter, period, off, sched, batch, inv_batch, relu_logits, true, true, true, true, a, g);
+  const DmlcWgradArgs w = make_wgrad_sgd(master, buf, idx, counter, period, off, sched, order, 0, cy, cx, groups2,
+                                         batch, true, false, true);
+  unsigned int* hand = reinterpret_cast<unsigned int*>(need_numel(buf, "bwd_hand", at::kInt, DMLC_HAND_WORDS).data_ptr<int>());
+  c10::DeviceGuard guard(master.device());
+  CHECK_HIP(dmlc_backward(&a, &g, &w, hand, stream_of(master)));
 }
 
 }  // namespace
@@ -814,55 +802,19 @@ TORCH_LIBRARY(dmlc, m) {
         "Tensor labels, Tensor idx, Tensor? counter, int period, float inv_batch, bool relu_logits, bool train, "
         "Tensor(a!) h1, Tensor(b!) h2, Tensor(c!) dl, Tensor(d!) dh1, Tensor(e!) dh2, Tensor(f!) loss_part, "
         "Tensor(g!) correct_part, Tensor(h!)? logits_out, int nvalid=-1, Tensor? step=None, Tensor(i!)? step_copy=None) -> ()");
-  m.def("fc_chain(Tensor p2, Tensor(a!) fc1n, Tensor(b!) h1part, Tensor b1, Tensor w2t, Tensor b2, Tensor w3t, "
-        "Tensor b3, Tensor w3d, Tensor labels, Tensor idx, Tensor? counter, int period, float inv_batch, "
-        "bool relu_logits, Tensor(c!) h1, Tensor(d!) h2, Tensor(e!) dl, Tensor(f!) dh1, Tensor(g!) dh2, "
-        "Tensor(h!) loss_part, Tensor(i!) correct_part, Tensor(j!) dp2, Tensor(k!) gw1, Tensor(l!) gw2, "
-        "Tensor(m!) gw3, Tensor(n!) gb1, Tensor(o!) gb2, Tensor(p!) gb3, bool fuse_sgd, float[] sched, "
-        "int nvalid, Tensor step, Tensor(q!)? step_copy, Tensor(r!) sync, Tensor(s!) err, bool dw_tasks=True, "
-        "Tensor? am2=None, Tensor? w2d=None, Tensor(t!)? dp1=None, Tensor(u!)? dy2=None, Tensor(v!)? fc2n=None) -> ()");
-  m.def("wgrad_sgd(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor dp1, Tensor am1, "
-        "Tensor p1, Tensor dy2, int groups2, Tensor xraw, Tensor(z!) bar, "
-        "Tensor(a!) master, Tensor(b!) grad, int mode, float grad_scale, int[] off, Tensor(r!) part1, Tensor(s!) partb1, "
-        "Tensor(t!) part2, Tensor(u!) partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
-        "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
-        "float decay_steps, bool staircase, Tensor(l!) ticket, Tensor loss_part, Tensor correct_part, "
-        "Tensor(m!) stats, Tensor(n!)? w2f8, Tensor(o!)? amax_w, Tensor(p!)? scale_w, int roles, "
-        "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
-        "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None, "
-        "Tensor[]? fc_acts=None, bool fc_sgd_done=False, Tensor[]? fp8=None) -> ()");
-  m.def("backward_fused_wgrad(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor dp1, Tensor am1, "
-        "Tensor p1, Tensor dy2, int groups2, Tensor xraw, Tensor(z!) bar, "
-        "Tensor(a!) master, Tensor(b!) grad, int mode, float grad_scale, int[] off, Tensor(r!) part1, Tensor(s!) partb1, "
-        "Tensor(t!) part2, Tensor(u!) partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
-        "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
-        "float decay_steps, bool staircase, Tensor(l!) ticket, Tensor loss_part, Tensor correct_part, "
-        "Tensor(m!) stats, Tensor(n!)? w2f8, Tensor(o!)? amax_w, Tensor(p!)? scale_w, int roles, "
-        "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
-        "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None, "
-        "Tensor[]? fc_acts=None, bool fc_sgd_done=False, Tensor[]? fp8=None) -> ()");
-  m.def("backward_fused(Tensor(w!) hand, Tensor p2, Tensor(a!) fc1n, Tensor(b!) h1part, Tensor b1, Tensor w2t, Tensor b2, "
-        "Tensor w3t, Tensor b3, Tensor w3d, Tensor labels, Tensor idx, Tensor? counter, int period, float inv_batch, "
-        "bool relu_logits, Tensor(c!) h1, Tensor(d!) h2, Tensor(e!) dl, Tensor(f!) dh1, Tensor(g!) dh2, "
-        "Tensor(h!) loss_part, Tensor(i!) correct_part, Tensor(j!) dp2, Tensor(k!) gw1, Tensor(l!) gw2, "
-        "Tensor(m!) gw3, Tensor(n!) gb1, Tensor(o!) gb2, Tensor(p!) gb3, bool fuse_sgd, float[] sched, "
-        "int nvalid, Tensor step, Tensor(q!)? step_copy, Tensor(r!) sync, Tensor(s!) err, bool dw_tasks=True, "
-        "Tensor? am2=None, Tensor? w2d=None, Tensor(t!)? dp1=None, Tensor(u!)? dy2=None, Tensor(v!)? fc2n=None) -> ()");
-  m.def("sgd(Tensor(a!) master, Tensor(b!) grad, int mode, float grad_scale, int[] off, Tensor part1, Tensor partb1, "
-        "Tensor part2, Tensor partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
-        "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
-        "float decay_steps, bool staircase, Tensor(l!) ticket, Tensor loss_part, Tensor correct_part, "
-        "Tensor(m!) stats, Tensor(n!)? w2f8, Tensor(o!)? amax_w, Tensor(p!)? scale_w, int roles, "
-        "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
-        "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None) -> ()");
-  m.def("xgmi_allreduce_sgd(int ctx, int blocks, bool bf16_wire, Tensor(a!) master, Tensor(b!) grad, int mode, "
-        "float grad_scale, int[] off, Tensor part1, Tensor partb1, "
-        "Tensor part2, Tensor partb2, Tensor(c!) w1f, Tensor(d!) w2f, Tensor(e!) w2d, Tensor(f!) fc1n, "
-        "Tensor(g!) fc2t, Tensor(h!) fc2n, Tensor(i!) fc3t, Tensor(j!) fc3d, Tensor(k!) step, float lr0, float decay, "
-        "float decay_steps, bool staircase, Tensor(l!) ticket, Tensor loss_part, Tensor correct_part, "
-        "Tensor(m!) stats, Tensor(n!)? w2f8, Tensor(o!)? amax_w, Tensor(p!)? scale_w, int roles, "
-        "bool finalize, int batch, Tensor(q!)? bidx=None, Tensor? order=None, float warmup=0.0, "
-        "bool fc1_fused=False, Tensor? step_rd=None, Tensor(v!)? xnext=None, Tensor? xdata=None) -> ()");
+  // the engine-level ops: master, the named buffers, then what differs from call to call
+  m.def("fc_chain(Tensor(a!) master, Dict(str, Tensor) buf, Tensor idx, Tensor? counter, int period, int[] off, "
+        "float[] sched, int batch, float inv_batch, bool relu_logits, bool fuse_sgd, bool dw_tasks, bool dgrad, "
+        "bool fc_sgd) -> ()");
+  m.def("sgd(Tensor(a!) master, Dict(str, Tensor) buf, int[] off, float[] sched, Tensor? order, int mode, int roles, "
+        "bool finalize, bool fc1_fused, int batch, bool prefetch) -> ()");
+  m.def("xgmi_allreduce_sgd(int ctx, int blocks, bool bf16_wire, Tensor(a!) master, Dict(str, Tensor) buf, int[] off, "
+        "float[] sched, Tensor? order, int batch, bool prefetch) -> ()");
+  m.def("wgrad_sgd(Tensor(a!) master, Dict(str, Tensor) buf, Tensor idx, Tensor? counter, int period, int[] off, "
+        "float[] sched, Tensor? order, int mode, int cy, int cx, int groups2, int batch, bool prefetch, bool fc_dw, "
+        "bool fc_sgd_done) -> ()");
+  m.def("backward_fused(Tensor(a!) master, Dict(str, Tensor) buf, Tensor idx, Tensor? counter, int period, int[] off, "
+        "float[] sched, Tensor? order, int cy, int cx, int groups2, int batch, float inv_batch, bool relu_logits) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
@@ -883,6 +835,5 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("sgd", &sgd);
   m.impl("xgmi_allreduce_sgd", &xgmi_allreduce_sgd);
   m.impl("wgrad_sgd", &wgrad_sgd);
-  m.impl("backward_fused_wgrad", &backward_fused_wgrad);
   m.impl("backward_fused", &backward_fused);
 }

@@ -1,6 +1,6 @@
 // The whole backward of the single-GPU bf16 step in ONE launch (128 < B <= 256): k_fc_chain's chain
 // phase and ticket, the conv2 input gradient of image blockIdx, then one role of k_wgrad in apply mode
-// -- the bodies of cnn_fc.hip, conv2_core.h and cnn_wgrad.hip, unchanged; this file adds the role map
+// -- the bodies of fc_chain_core.h, conv2_core.h and wgrad_core.h, unchanged; this file adds the role map
 // and the per-image hand-offs between them, no arithmetic.  Bitwise the two launches' results: every
 // role keeps its image order, so every slab sums in the same order.
 //
@@ -25,13 +25,13 @@
 // word is posted from inside the dgrad core, behind its first barrier: that barrier waits vmcnt(0)
 // for the kernel-row-0 slice anyway, so draining the dY2 stores there puts no wait in front of the
 // weight-slice loads (posting from the storing waves right after the stores would).  The dP1 word
-// follows the drained dP1 stores.  Consumers: see cnn_wgrad.hip (INL).
+// follows the drained dP1 stores.  Consumers: see wgrad_core.h (INL).
 //
 // Liveness: every block finishes ALL its producing work (chain tasks, ticket, dgrad) before its first
 // image wait, no chain seam depends on a weight-gradient role, and the wgrad barriers are met only by
 // blocks past their dgrad -- the wait graph is acyclic with 256 co-resident blocks (host-checked).
 //
-// What the merged launch must order that a launch boundary ordered before (all in cnn_wgrad.hip, INL):
+// What the merged launch must order that a launch boundary ordered before (all in wgrad_core.h, INL):
 //  * the conv2 SGD rewrites w2d, which every dgrad reads through its whole core: conv2_apply also
 //    waits for every image's dP1 word;
 //  * the loss / accuracy partials and the labels' batch rows (bidx) belong to head blocks of this
@@ -39,10 +39,8 @@
 //    batch rows move behind the conv1 barrier wait;
 //  * the fc SGD roles would read the dW tiles' flat gradient: not supported here -- the chain applies
 //    every fc SGD in the tiles' epilogues (fuse_sgd == 2, fc_done; host-checked).
-#define DMLC_FC_BODY_ONLY
-#define DMLC_WGRAD_BODY_ONLY
-#include "cnn_fc.hip"
-#include "cnn_wgrad.hip"
+#include "fc_chain_core.h"
+#include "wgrad_core.h"
 
 namespace dmlc {
 

@@ -19,7 +19,7 @@
 // weights (w2d8, quantised by the SGD kernel with the same scale as w2f8) and the pool2/ReLU-backward
 // gradient dY2 quantised per IMAGE with sy = 448 / amax(dY2 of that image), reduced in-block from the
 // values the block just produced, rounded down to a power of two (r6); the quantised dY2 and its
-// scale are also stored (dy8out, sy_img) for the fp8 conv2 weight gradient (cnn_wgrad.hip w2_fp8_main),
+// scale are also stored (dy8out, sy_img) for the fp8 conv2 weight gradient (wgrad_core.h w2_fp8_main),
 // as the forward stores its quantised input and sx (x8out, sx_out).
 #include "conv_common.h"
 

@@ -1,6 +1,6 @@
 // Building blocks of the fully-connected chain shared by the persistent fc-chain launch
 // (cnn_fc.hip) and the weight-gradient launch (cnn_wgrad.hip, apply mode: the fc weight gradients
-// and their SGD run in the conv1 blocks' idle time there).  See cnn_fc.hip for the design.
+// and their SGD run in the conv1 blocks' idle time there).  See fc_chain_core.h for the design.
 #pragma once
 #include "common.h"
 #include "api.h"

@@ -113,13 +113,10 @@ def build(hip: bool = True, rt: bool = True, jobs: int | None = None) -> dict:
         if TIMING:   # the stamp buffer is one __device__ symbol shared by every kernel TU
             hip_flags += ["-DDMLC_TIMING", "-fgpu-rdc"]
         hip_flags += VARIANT_FLAGS
-        # sources that include other sources (cnn_bwd.hip: the bodies of the two launches it merges)
-        hip_includes = {"cnn_bwd.hip": ["cnn_fc.hip", "cnn_wgrad.hip"]}
         for src in sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip"))):
             o = os.path.join(OBJ_DIR, os.path.basename(src) + (f"{_SUFFIX.replace('_', '.')}.o" if _SUFFIX else ".o"))
             hip_objs.append(o)
-            deps = headers + [os.path.join(CSRC, "kernels", d) for d in hip_includes.get(os.path.basename(src), [])]
-            jobs_list.append((src, deps, o, [hipcc], hip_flags))
+            jobs_list.append((src, headers, o, [hipcc], hip_flags))
         bheaders = headers + glob.glob(os.path.join(CSRC, "bindings", "*.h"))
         for bsrc in sorted(glob.glob(os.path.join(CSRC, "bindings", "*.cpp"))):
             o = os.path.join(OBJ_DIR, os.path.basename(bsrc) + ".o")

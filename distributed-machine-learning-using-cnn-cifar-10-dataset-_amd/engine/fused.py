@@ -46,6 +46,11 @@ co-residency-dependent launch off without code changes (a training run builds th
 ``variant``): DMLC_FC_FUSED=0 (the fc chain), DMLC_WGRAD_SGD=0 (the in-launch SGD / slab reduction of
 the wgrad launch) and DMLC_FWD12_SPLIT=0 (the B <= 128 forward whose two workgroups per image wait on
 each other).
+
+Bindings: the launches that touch most of the engine's state (fc_chain, sgd, xgmi_allreduce_sgd,
+wgrad_sgd and backward_fused, the whole backward as one call) take ``self.buf``, the device buffers
+keyed by attribute name, plus the switches that differ from call to call; the binding checks every
+buffer it reads by name and keeps no state between calls (csrc/bindings/torch_ops.cpp).
 """
 from __future__ import annotations
 
@@ -108,6 +113,12 @@ TICKET_WORDS = 9 * 32
 WBAR_WORDS = 20 * 32
 # int32 words of the one-launch backward's per-image hand-off words (DMLC_HAND_WORDS)
 HAND_WORDS = 2 * 256 * 32
+# the engine attributes the dict-taking ops read by name (FusedCifarEngine.buf)
+BUF_NAMES = ("master", "grad", "grad16", "part1", "partb1", "part2", "partb2", "w1f", "w2f", "w2d", "fc1n", "fc2t",
+             "fc2n", "fc3t", "fc3d", "step_t", "step_sgd", "ticket", "loss_part", "correct_part", "stats", "bidx",
+             "xraw", "data", "labels", "p1", "p2", "am1", "am2", "dp1", "dp2", "dy2", "h1part8", "h1", "h2", "dl",
+             "dh1", "dh2", "fc_sync", "wbar", "bwd_hand", "w2f8", "amax_w", "scale_w", "p1f8", "dy2f8", "sx8",
+             "sy_img")
 SEG = {M.short(s.name): s for s in M.PARAM_SPECS}
 
 
@@ -315,8 +326,6 @@ class FusedCifarEngine:
         self.grad16 = None
         if (self.dp and comm_dtype == "bf16" and self.xgmi is None and self.fc_fused and bool(V["grad16"])):
             self.grad16 = torch.zeros(self.master.numel(), dtype=torch.bfloat16, device=dev)
-        self.gv_chain = ({k: self.grad16[s.offset:s.offset + s.numel] for k, s in SEG.items()}
-                         if self.grad16 is not None else gv)
 
         # grouped GEMM problem lists (the three-launch fc path)
         self._fc1_fwd = dict(A=[self.p2.view(B, 2304)], B=[self.fc1n], C=[self.h1part], bias=[None],
@@ -461,6 +470,11 @@ class FusedCifarEngine:
             self.comm_info.update(schedule=dp_schedule, backend=self._backend(),
                                   captured_comm=bool(self.capture_comm or self.xgmi is not None),
                                   grad_dtype="bf16" if self.grad16 is not None else "fp32")
+        # the device buffers by attribute name, for the ops that take them as one dict (csrc/bindings/
+        # torch_ops.cpp: fc_chain, sgd, xgmi_allreduce_sgd, wgrad_sgd, backward_fused); a buffer this
+        # configuration does not have is an absent key.  Nothing rebinds these attributes afterwards
+        # (evaluate() swaps data / labels only around eval forwards, which take them as arguments).
+        self.buf = {k: t for k in BUF_NAMES if (t := getattr(self, k, None)) is not None}
         self.host_step = 0
         self._sync_bidx()
         self.refresh_shadows()
@@ -556,8 +570,8 @@ class FusedCifarEngine:
 
     def _gemm(self, f, sgd: bool = False):
         if sgd:
-            sched = [self.lr0, self.decay, self.decay_steps, 1.0 if self.staircase else 0.0, self.warmup, 1.0]
-            self.ops.gemm_grouped(f["A"], f["B"], f["C"], f["bias"], f["params"], self.step_t, self.fc1n, sched)
+            self.ops.gemm_grouped(f["A"], f["B"], f["C"], f["bias"], f["params"], self.step_t, self.fc1n,
+                                  self._sched())
         else:
             self.ops.gemm_grouped(f["A"], f["B"], f["C"], f["bias"], f["params"], self.step_t)
 
@@ -575,28 +589,15 @@ class FusedCifarEngine:
             raise RuntimeError("_fc_chain must follow a training _forward")
         if self._dgrad_done:
             raise RuntimeError("the previous fc chain's conv backward never ran")
-        self.ops.fc_chain(*self._fc_chain_args(fused_sgd))
-        self._dgrad_done = self.fc_dgrad
-
-    def _fc_chain_args(self, fused_sgd: bool) -> tuple:
         idx, counter, period = self._fc_src
         self._fc_src = None
-        p, gv = self.pv, self.gv
-        sched = [self.lr0, self.decay, self.decay_steps, 1.0 if self.staircase else 0.0, self.warmup, 1.0]
-        all_sgd = fused_sgd and self.fc_sgd_in_chain
-        if not fused_sgd:
-            gv = self.gv_chain                   # (bf16 views on the RCCL bf16 wire)
-        g = p if all_sgd else gv                 # every fc SGD here: the master views, else the gradients
-        return (self.p2.view(self.B, 2304), self.fc1n, self.h1part8, p["full_bias_1"], self.fc2t,
-                p["full_bias_2"], self.fc3t, p["full_bias_3"], self.fc3d, self.labels, idx, counter, period,
-                1.0 / (self.Bv * self.world_size), self.relu_logits, self.h1, self.h2, self.dl, self.dh1,
-                self.dh2, self.loss_part, self.correct_part, self.dp2.view(self.B, 2304),
-                p["full_weight_1"] if fused_sgd else gv["full_weight_1"], g["full_weight_2"],
-                g["full_weight_3"], g["full_bias_1"], g["full_bias_2"], g["full_bias_3"], fused_sgd,
-                sched, self.Bv, self.step_t, self.step_sgd, self.fc_sync, self.wbar[10 * 32:10 * 32 + 1],
-                not (fused_sgd and self.fc_dw_in_wgrad),
-                *((self.am2, self.w2d, self.dp1, self.dy2) if self.fc_dgrad else (None, None, None, None)),
-                self.fc2n if all_sgd else None)
+        # the binding picks the flat views the chain writes from the switches: master where an SGD is
+        # fused (fc1: fuse_sgd, the rest: fc_sgd), else grad (grad16 on the RCCL bf16 wire)
+        self.ops.fc_chain(self.master, self.buf, idx, counter, period, SEG_OFF, self._sched(), self.Bv,
+                          1.0 / (self.Bv * self.world_size), self.relu_logits, fuse_sgd=fused_sgd,
+                          dw_tasks=not (fused_sgd and self.fc_dw_in_wgrad), dgrad=self.fc_dgrad,
+                          fc_sgd=fused_sgd and self.fc_sgd_in_chain)
+        self._dgrad_done = self.fc_dgrad
 
     def _backward_fused(self):
         """The training step's whole backward + SGD as one launch (bwd_fused; cnn_bwd.hip), for the
@@ -605,13 +606,11 @@ class FusedCifarEngine:
             raise RuntimeError("_backward_fused must follow a training _forward")
         if self._dgrad_done:
             raise RuntimeError("the previous fc chain's conv backward never ran")
-        fc = self._fc_chain_args(True)
-        # (an op schema holds at most 64 arguments: the first call only stages the wgrad + SGD
-        # arguments on the host, the second launches)
-        self.ops.backward_fused_wgrad(self.data, self.bidx, None, 1, self.cy, self.cx, self.dp1, self.am1,
-                                      self.p1, self.dy2, self.groups2, self.xraw, self.wbar,
-                                      *self._sgd_args(mode=0, fc1_fused=True), fc_acts=None, fc_sgd_done=True)
-        self.ops.backward_fused(self.bwd_hand, *fc)
+        idx, counter, period = self._fc_src
+        self._fc_src = None
+        self.ops.backward_fused(self.master, self.buf, idx, counter, period, SEG_OFF, self._sched(),
+                                self.order_desc, self.cy, self.cx, self.groups2, self.Bv,
+                                1.0 / (self.Bv * self.world_size), self.relu_logits)
 
     def _conv_backward(self, src=None, apply: bool = False, reduce: bool = False):
         """apply: + the whole SGD in the wgrad launch (single GPU); reduce: + the conv slab reduction
@@ -630,32 +629,28 @@ class FusedCifarEngine:
         else:
             o.conv2_dgrad(self.dp2, self.am2, self.w2d, self.dp1, self.dy2)
         if apply or reduce:
-            fc_acts = None
-            if apply and self.fc_dw_in_wgrad:
-                fc_acts = [self.p2.view(self.B, 2304), self.h1, self.h2, self.dl, self.dh1, self.dh2]
-            o.wgrad_sgd(self.data, idx, counter, period, self.cy, self.cx, self.dp1, self.am1, self.p1, self.dy2,
-                        self.groups2, self.xraw, self.wbar,
-                        *(self._sgd_args(mode=0, fc1_fused=True) if apply else self._sgd_args(mode=1)),
-                        fc_acts=fc_acts, fc_sgd_done=bool(apply and self.fc_sgd_in_chain), **self._w8)
+            mode = 0 if apply else 1
+            o.wgrad_sgd(self.master, self.buf, idx, counter, period, SEG_OFF, self._sched(), self.order_desc, mode,
+                        self.cy, self.cx, self.groups2, self.Bv, prefetch=self._prefetch_next(mode),
+                        fc_dw=bool(apply and self.fc_dw_in_wgrad), fc_sgd_done=bool(apply and self.fc_sgd_in_chain))
             return
         o.wgrad(self.data, idx, counter, period, self.cy, self.cx, self.dp1, self.am1,
                 self.part1, self.partb1, self.p1, self.dy2, self.part2, self.partb2, self.groups2, self.xraw,
                 **self._w8)
 
-    def _sgd_args(self, mode: int, scale: float = 1.0, roles: int = 0, finalize: bool = True,
-                  fc1_fused: bool = False) -> tuple:
-        gflat = self.grad16 if (self.grad16 is not None and mode in (1, 2)) else self.grad
-        return (self.master, gflat, mode, scale, SEG_OFF, self.part1, self.partb1, self.part2, self.partb2,
-                self.w1f, self.w2f, self.w2d, self.fc1n, self.fc2t, self.fc2n, self.fc3t, self.fc3d,
-                self.step_t, self.lr0, self.decay, self.decay_steps, self.staircase, self.ticket,
-                self.loss_part, self.correct_part, self.stats,
-                *((self.w2f8, self.amax_w, self.scale_w) if self.fp8 else (None, None, None)),
-                roles, finalize, self.Bv, self.bidx, self.order_desc, self.warmup, fc1_fused,
-                None if mode == 3 else self.step_sgd,
-                *((self.xraw, self.data) if self.xraw_prefetch and mode in (0, 2) and finalize else (None, None)))
+    def _sched(self, scale: float = 1.0) -> list:
+        """{lr0, decay, decay_steps, staircase, warmup, grad_scale} of the SGD ops and the fc chain."""
+        return [self.lr0, self.decay, self.decay_steps, 1.0 if self.staircase else 0.0, self.warmup, scale]
+
+    def _prefetch_next(self, mode: int, finalize: bool = True) -> bool:
+        """Whether an SGD of this mode also gathers the next step's raw images into xraw."""
+        return bool(self.xraw_prefetch and mode in (0, 2) and finalize)
 
     def _sgd(self, mode: int, scale: float = 1.0, roles: int = 0, finalize: bool = True, fc1_fused: bool = False):
-        self.ops.sgd(*self._sgd_args(mode, scale, roles, finalize, fc1_fused))
+        # (the binding takes grad16 for the flat gradient in modes 1 / 2 where the engine has one, and
+        # the head's step copy in every mode but 3)
+        self.ops.sgd(self.master, self.buf, SEG_OFF, self._sched(scale), self.order_desc, mode, roles, finalize,
+                     fc1_fused, self.Bv, self._prefetch_next(mode, finalize))
 
     @property
     def barriers_in_use(self) -> bool:
@@ -862,7 +857,8 @@ class FusedCifarEngine:
         seg[0]()
         n = self.master.numel()
         if self.comm_sgd:           # (xGMI: the whole step is one graph, seg is never a replay list)
-            self.xgmi.all_reduce_sgd(self._sgd_args(mode=2), blocks=self._comm_blocks)
+            self.xgmi.all_reduce_sgd(self.master, self.buf, SEG_OFF, self._sched(), self.order_desc, self.Bv,
+                                     self._prefetch_next(2), blocks=self._comm_blocks)
             return
         if self.xgmi is not None:
             self.xgmi.all_reduce(0, n)
