@@ -180,7 +180,8 @@ __global__ __launch_bounds__(HT, 1) void k_head(DmlcHeadArgs a) {
       float se = 0.f;
 #pragma unroll
       for (int j = 0; j < 10; ++j) se += __expf(lg[lane][j] - m);
-      const float lse = m + __logf(se);
+      const float lm = __logf(se);
+      const float lse = m + lm;
       loss = vr * (lse - lg[lane][label]);
       corr = vr * (am == label ? 1.f : 0.f);
       if (a.logits_out) {
@@ -188,11 +189,21 @@ __global__ __launch_bounds__(HT, 1) void k_head(DmlcHeadArgs a) {
         for (int j = 0; j < 10; ++j) a.logits_out[b * 10 + j] = lg[lane][j];
       }
       if (a.train) {
+        // softmax - onehot without cancellation: p_j = exp((l_j - m) - log se) keeps the small
+        // probabilities of a saturated row to fp32 relative accuracy (l_j - lse loses ulp(m)), and the
+        // label's entry is -(the sum of the others), not p_label - 1 (absolute error ulp(1) against an
+        // entry that can be 1e-6 and smaller): every row is relatively accurate and sums to zero
+        float pj[10], others = 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+          pj[j] = __expf((lg[lane][j] - m) - lm);
+          if (j != label) others += pj[j];
+        }
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
           float d = 0.f;
           if (j < 10) {
-            d = (__expf(lg[lane][j] - lse) - (j == label ? 1.f : 0.f)) * a.inv_batch * vr;
+            d = (j == label ? -others : pj[j]) * a.inv_batch * vr;
             if (a.relu_logits && !(lg[lane][j] > 0.f)) d = 0.f;
           }
           dls[lane * DL_LD + j] = (bf16)d;

@@ -260,8 +260,19 @@ DEV void head_task(const DmlcFcArgs& a, int hb, char* smem, int tid) {
     for (int i = 0; i < 4; ++i) se += 4 * g + i < 10 ? __expf(v[i] - m) : 0.f;
     se += __shfl_xor(se, 16);
     se += __shfl_xor(se, 32);
-    const float lse = m + __logf(se);
+    const float lm = __logf(se);
+    const float lse = m + lm;
     const int lab = __shfl(label, li);          // wave 7 lane r < RB loaded row r's label
+    // softmax - onehot without cancellation (as cnn_head.hip): p = exp((l - m) - log se), and the
+    // label's entry is -(the sum of the other classes' p) instead of p_label - 1
+    float pv[4], others = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      pv[i] = __expf((v[i] - m) - lm);
+      if (4 * g + i < 10 && 4 * g + i != lab) others += pv[i];
+    }
+    others += __shfl_xor(others, 16);
+    others += __shfl_xor(others, 32);
     const bool rowok = li < RB;
     const float vr = rowok && r0 + li < a.nvalid ? 1.f : 0.f;
     float loss = 0.f;
@@ -275,7 +286,7 @@ DEV void head_task(const DmlcFcArgs& a, int hb, char* smem, int tid) {
         const int c = 4 * g + i;
         float d = 0.f;
         if (c < 10) {
-          d = (__expf(v[i] - lse) - (c == lab ? 1.f : 0.f)) * a.inv_batch * vr;
+          d = (c == lab ? -others : pv[i]) * a.inv_batch * vr;
           if (a.relu_logits && !(v[i] > 0.f)) d = 0.f;
         }
         d4[i] = (bf16)d;

@@ -16,12 +16,25 @@ from dmlc.engine.fused import FusedCifarEngine
 from dmlc.models import cifar_cnn as M
 
 pytestmark = pytest.mark.gpu
+# asserted on the whole tensor and, for every output with a batch dimension, on its worst single image
+# (what no tolerance can check -- argmax bytes, borders, crops, single channels -- is
+# tests/test_cnn_exact_gpu.py)
 TOL = 1e-2
 
 
 def _rel(a, b):
     a, b = a.detach().float(), b.detach().float()
     return float((a - b).norm() / (b.norm() + 1e-12))
+
+
+def _rel_img(a, b):
+    """Worst image: the maximum over the batch dimension of the per-image relative error.  An image
+    whose reference is exactly zero (a padding row's gradient) must be exactly zero in the kernel."""
+    a = a.detach().double().reshape(a.shape[0], -1)          # fp64 norms: a saturated row of dlogits is ~1e-14
+    b = b.detach().double().reshape(b.shape[0], -1)
+    num, den = (a - b).norm(dim=1), b.norm(dim=1)
+    r = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0))
+    return float(r.max())
 
 
 def _pool_bwd(dp, am, H):
@@ -36,9 +49,21 @@ def _pool_bwd(dp, am, H):
 
 
 def cnn_local_errors(eng, data, labels, idx):
-    """{check: rel error} for every kernel of one training step on dataset rows ``idx``."""
+    """({check: rel error}, {check: {worst_image, floor}}) for every kernel of one training step on
+    dataset rows ``idx``.  The second dict covers every output with a batch dimension: the worst
+    per-image relative error (a whole-tensor norm hides one wrong image) next to its floor, the fp32
+    reference rounded to bf16 against itself, per image.  The gradients are compared over the whole
+    kernel batch: their padding rows (>= Bv) have an exactly zero reference."""
     dev = eng.device
     B = eng.Bv
+    img = {}
+
+    def per_image(name, a, b):
+        a = a.detach().float()
+        b = b.detach().float()                            # (an fp64 reference: rounded to fp32, per element)
+        if a.shape[0] > b.shape[0]:                      # the padding rows of a gradient: zero
+            b = torch.cat([b, b.new_zeros(a.shape[0] - b.shape[0], *b.shape[1:])])
+        img[name] = {"worst_image": _rel_img(a, b), "floor": _rel_img(b.to(torch.bfloat16), b)}
     eng.keep_dp1 = True                  # the fused dgrad keeps dp1 in LDS unless asked for a copy
     eng.compute_gradients(idx=idx)
     torch.cuda.synchronize()
@@ -57,9 +82,11 @@ def cnn_local_errors(eng, data, labels, idx):
     w2 = bfw["conv2_kernel"].permute(3, 2, 0, 1)
     y1 = F.relu(F.conv2d(nchw(x), w1, p["conv1_bias"], padding=2))
     out["conv1_fwd"] = _rel(nchw(eng.p1[:B]), M.tf_same_maxpool_3x3s2(y1))
+    per_image("conv1_fwd", nchw(eng.p1[:B]), M.tf_same_maxpool_3x3s2(y1))
     p1 = nchw(eng.p1[:B])
     y2 = F.relu(F.conv2d(p1, w2, p["conv2_bias"], padding=2))
     out["conv2_fwd"] = _rel(nchw(eng.p2[:B]), M.tf_same_maxpool_3x3s2(y2))
+    per_image("conv2_fwd", nchw(eng.p2[:B]), M.tf_same_maxpool_3x3s2(y2))
     # argmax bytes: 255 exactly where the pooled (post-ReLU) value is 0
     out["argmax_mask"] = float(((eng.am2[:B] == 255) != (eng.p2[:B] == 0)).float().mean())
 
@@ -86,9 +113,21 @@ def cnn_local_errors(eng, data, labels, idx):
     out["head_dh2"] = _rel(dh2, (dl @ bfw["full_weight_3"].t()) * (h2 > 0))
     dh1 = eng.dh1[:B].float()
     out["head_dh1"] = _rel(dh1, (dh2 @ bfw["full_weight_2"].t()) * (h1 > 0))
+    per_image("head_h1", h1, F.relu(h1pre + p["full_bias_1"]))
+    per_image("head_h2", h2, F.relu(h1 @ bfw["full_weight_2"] + p["full_bias_2"]))
+    # per row, softmax - onehot needs an fp64 reference (from the same fp32 logits): on a saturated row
+    # the label's entry p - 1 cancels, so fp32 autograd itself is off by ulp(1) / |row| -- 79 % on the
+    # worst row of these batches, whose dlogits are ~1e-12 -- and so was the head kernel until it took
+    # the label's entry as -(the sum of the others): 0.225 measured against fp32 autograd at B = 64
+    lg64 = lg.detach().double()
+    dl64 = (torch.softmax(lg64, 1) - F.one_hot(y, 10)) / B
+    per_image("head_dlogits", eng.dl[:, :10], dl64 * (logits.detach() > 0) if eng.relu_logits else dl64)
+    per_image("head_dh2", eng.dh2, (dl @ bfw["full_weight_3"].t()) * (h2 > 0))
+    per_image("head_dh1", eng.dh1, (dh2 @ bfw["full_weight_2"].t()) * (h1 > 0))
 
     # grouped fc backward GEMM: dp2 and the fc weight / bias gradients
     out["fc1_dgrad"] = _rel(eng.dp2[:B].reshape(B, 2304), dh1 @ bfw["full_weight_1"].t())
+    per_image("fc1_dgrad", eng.dp2.reshape(eng.B, 2304), dh1 @ bfw["full_weight_1"].t())
     out["fc1_wgrad"] = _rel(g["full_weight_1"], p2.t() @ dh1)
     out["fc2_wgrad"] = _rel(g["full_weight_2"], h1.t() @ dh2)
     out["fc3_wgrad"] = _rel(g["full_weight_3"], h2.t() @ dl)
@@ -99,11 +138,13 @@ def cnn_local_errors(eng, data, labels, idx):
     # conv2_dgrad: pool2/ReLU backward (-> dy2) and the conv2 input gradient (-> dp1)
     dy2_ref = _pool_bwd(eng.dp2[:B], eng.am2[:B], 12)
     out["pool2_bwd"] = _rel(eng.dy2[:B].view(B, 12, 12, 64), dy2_ref)
+    per_image("pool2_bwd", eng.dy2.view(eng.B, 12, 12, 64), dy2_ref)
     dy2 = nchw(eng.dy2[:B].view(B, 12, 12, 64))
     xin = p1.clone().requires_grad_(True)
     wv = w2.clone().requires_grad_(True)
     F.conv2d(xin, wv, None, padding=2).backward(dy2)
     out["conv2_dgrad"] = _rel(nchw(eng.dp1[:B]), xin.grad)
+    per_image("conv2_dgrad", nchw(eng.dp1), xin.grad)
 
     # wgrad: conv2 weight/bias gradients from the kernel's p1 and dy2; conv1 from its dp1 / am1
     out["conv2_wgrad"] = _rel(g["conv2_kernel"], wv.grad.permute(2, 3, 1, 0))
@@ -127,7 +168,7 @@ def cnn_local_errors(eng, data, labels, idx):
         _rel(eng.fc1n_current(), nb["full_weight_1"]), _rel(eng.fc2n, nb["full_weight_2"]),
         _rel(eng.fc2t, nb["full_weight_2"].t()), _rel(eng.fc3t[:10], nb["full_weight_3"].t()),
         _rel(eng.w2f.view(64, 25, 64), nb["conv2_kernel"].reshape(25, 64, 64).permute(2, 0, 1)))
-    return out
+    return out, img
 
 
 # (batch, ReLU on the logits, conv_split, conv1_split): the channel-split kernels (cnn_split.hip) at
@@ -143,14 +184,23 @@ def test_every_kernel_matches_fp32_on_its_own_inputs(B, relu_logits, split, spli
     eng = FusedCifarEngine(B, data, labels, seed=4, lr=0.01, relu_logits=relu_logits, conv_split=split,
                            conv1_split=split1)
     idx = eng.batch_indices(0)
-    errs = cnn_local_errors(eng, data, labels, idx)
+    errs, img = cnn_local_errors(eng, data, labels, idx)
     os.makedirs("gpurun_out", exist_ok=True)
     with open(f"gpurun_out/cnn_local_errors_b{B}_s{split}{split1}.json", "w") as f:
-        json.dump({k: float(f"{v:.3e}") for k, v in errs.items()}, f, indent=1)
+        json.dump(dict({k: float(f"{v:.3e}") for k, v in errs.items()},
+                       per_image={k: {n: float(f"{x:.3e}") for n, x in v.items()} for k, v in img.items()}),
+                  f, indent=1)
     assert errs["argmax_mask"] == 0.0
     bad = {k: v for k, v in errs.items() if not v <= TOL}
     assert not bad, (bad, errs)
     assert errs["sgd_master"] < 1e-6 and errs["head_loss"] < 1e-4, errs
+    # the worst single image of every batched output: the same bound as the whole tensor (bf16 rounding
+    # is a per-element relative error, so the per-image floor is the whole-tensor one, ~2e-3); a
+    # non-zero padding row of a gradient reads inf
+    assert set(img) == {"conv1_fwd", "conv2_fwd", "head_h1", "head_h2", "head_dlogits", "head_dh2", "head_dh1",
+                        "fc1_dgrad", "pool2_bwd", "conv2_dgrad"}
+    bad = {k: v for k, v in img.items() if not v["worst_image"] <= TOL}
+    assert not bad, (bad, img)
 
 
 @pytest.mark.parametrize("relu_logits,lr", [(True, 1e-5), (False, 1e-4)])
