@@ -552,9 +552,9 @@ void make_fc(const Tensor& master, const Buf& buf, const Tensor& idx, const c10:
   a.staircase = sched[3] != 0.0; a.warmup = (float)sched[4]; a.grad_scale = (float)sched[5];
   a.step = need_numel(buf, "step_t", at::kLong, 1).data_ptr<int64_t>();
   a.step_copy = need_numel(buf, "step_sgd", at::kLong, 1).data_ptr<int64_t>();
-  a.sync = reinterpret_cast<unsigned int*>(need_min(buf, "fc_sync", at::kInt, 212 * 32).data_ptr<int>());   // fc_common.h SY_END
-  // the sticky error word is the wgrad barriers' (wbar[10 * 32])
-  a.err = reinterpret_cast<unsigned int*>(need_numel(buf, "wbar", at::kInt, DMLC_WBAR_WORDS).data_ptr<int>()) + 10 * 32;
+  a.sync = reinterpret_cast<unsigned int*>(need_min(buf, "fc_sync", at::kInt, DMLC_FC_SYNC_WORDS).data_ptr<int>());
+  // the sticky error word is the wgrad barriers' (wbar[DMLC_WBAR_ERR])
+  a.err = reinterpret_cast<unsigned int*>(need_numel(buf, "wbar", at::kInt, DMLC_WBAR_WORDS).data_ptr<int>()) + DMLC_WBAR_ERR;
   memset(&g, 0, sizeof(g));
   if (dgrad) {
     // one image per workgroup; am2 / w2d / dp1 / dy2 come together (need() names a missing one)
@@ -741,7 +741,7 @@ DmlcWgradArgs make_wgrad_sgd(const Tensor& master, const Buf& buf, const Tensor&
     f.fuse_sgd = 2; f.dw_tasks = 1;
     f.lr0 = a.sgd.lr0; f.decay = a.sgd.decay; f.decay_steps = a.sgd.decay_steps; f.staircase = a.sgd.staircase;
     f.warmup = a.sgd.warmup; f.grad_scale = a.sgd.grad_scale;
-    f.err = a.bar + 10 * 32;
+    f.err = a.bar + DMLC_WBAR_ERR;
     a.fc_in_launch = 1;
   }
   return a;

@@ -9,6 +9,8 @@
 
 // uints in the arrival-ticket buffer of the SGD launches (two-level counters, common.h last_arrival)
 #define DMLC_TICKET_WORDS (9 * 32)
+// uints of the fc chain's sync words (DmlcFcArgs::sync; fc_common.h SY_END counters, one 128-B line each)
+#define DMLC_FC_SYNC_WORDS (212 * 32)
 
 extern "C" {
 
@@ -283,9 +285,10 @@ struct DmlcSgdArgs {
 // slab family meet at a sub-grid barrier (bar: DMLC_WBAR_WORDS zeroed uints), reduce their share of
 // the slabs in the SGD kernel's order and apply the update (sgd: mode 0, fc1_fused, step_rd = the
 // head's step copy); the conv1 blocks also run the fc roles, publish the stats and bump global_step.
-// No SGD launch follows.  bar[10 * 32] is a sticky error word (a barrier that timed out); from
+// No SGD launch follows.  bar[DMLC_WBAR_ERR] is a sticky error word (a barrier that timed out); from
 // bar[11 * 32]: one claim word per conv2 slab chunk (the conv1 "helpers", cnn_wgrad.hip).
 #define DMLC_WBAR_WORDS (20 * 32)
+#define DMLC_WBAR_ERR (10 * 32)
 struct DmlcWgradArgs {
   DmlcConv1WgradArgs w1;
   DmlcConv2WgradArgs w2;

@@ -120,7 +120,7 @@ extern "C" hipError_t dmlc_backward(const DmlcFcArgs* a, const DmlcConv2DgradArg
   if (!w->apply || g.mode != 0 || w->fc_in_launch || !w->fc_done || g.w2f8 || w->w2.x8 || g.grad16)
     return hipErrorInvalidValue;
   if (w->w1.g1 + 4 * w->w2.g2 != FC_BLOCKS || w->w1.g1 % 8 || w->w2.g2 % 8 || w->w1.g1 > a->B) return hipErrorInvalidValue;
-  if (w->w1.B != a->B || w->w2.B != a->B || g.step != a->step || w->bar + 10 * 32 != a->err) return hipErrorInvalidValue;
+  if (w->w1.B != a->B || w->w2.B != a->B || g.step != a->step || w->bar + DMLC_WBAR_ERR != a->err) return hipErrorInvalidValue;
   if (w->w1.dp1 != dg->dp1 || w->w2.dy2 != dg->dy2 || g.w2d != dg->wd || g.loss_part != a->loss_part ||
       g.correct_part != a->correct_part || g.nhead != a->B / FC_RB)
     return hipErrorInvalidValue;

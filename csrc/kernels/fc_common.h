@@ -50,7 +50,7 @@ DEV unsigned* epochW(const DmlcFcArgs& a) { return a.sync + 32 * 9; }
 // fc1 forward task (m, nt, s) -> word (m, nt): FC_S arrivals each; the head blocks of row tile m wait
 // for the tile's 6 words
 constexpr int SY_A = 28, SY_B = SY_A + 24, SY_D = SY_B + 16, SY_END = SY_D + 2 * 4 * 18;
-static_assert(SY_END == 212, "engine/fused.py fc_sync and the binding size the sync words");
+static_assert(SY_END * 32 == DMLC_FC_SYNC_WORDS, "the engine (engine/plan.py FC_SYNC_WORDS) and the binding size the sync words");
 DEV unsigned* cntA(const DmlcFcArgs& a, int m, int nt) { return a.sync + 32 * (SY_A + 6 * m + nt); }
 DEV Seam seamA(const DmlcFcArgs& a, int m) { return Seam{cntA(a, m, 0), 6, (unsigned)FC_S}; }
 // head block hb (row tile m = hb >> 4) -> word (m, hb & 3): a quarter of the tile's head blocks each

@@ -41,7 +41,9 @@ the head gives padding rows zero loss weight (their gradients are exactly zero).
 
 Variants: every default below is the measured-fastest path of its configuration; the alternatives
 that stay are the bitwise references the tests compare against, selected with the ``variant``
-dict of the constructor (VARIANT_DEFAULTS).  Three environment switches turn a persistent,
+dict of the constructor (VARIANT_DEFAULTS).  Which path a configuration takes is decided by the pure
+function engine/plan.py plan_step; the constructor collects its inputs, keeps the result as
+``self.plan`` and allocates from it.  Three environment switches turn a persistent,
 co-residency-dependent launch off without code changes (a training run builds the engine without a
 ``variant``): DMLC_FC_FUSED=0 (the fc chain), DMLC_WGRAD_SGD=0 (the in-launch SGD / slab reduction of
 the wgrad launch) and DMLC_FWD12_SPLIT=0 (the B <= 128 forward whose two workgroups per image wait on
@@ -54,6 +56,7 @@ buffer it reads by name and keeps no state between calls (csrc/bindings/torch_op
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from typing import Dict, List, Optional
@@ -65,6 +68,8 @@ from ..parallel.dist import quiesce_for_capture
 from ..data.order import OrderSpec
 from ..models import cifar_cnn as M
 from ..ops import _ext
+from .plan import (ERR_WORD, FC_SYNC_WORDS, HAND_WORDS, TICKET_WORDS, VARIANT_DEFAULTS, WBAR_WORDS,  # noqa: F401
+                   head_rows, plan_step)
 
 OPS = None
 
@@ -78,41 +83,6 @@ def _ops():
 
 
 SEG_OFF = [s.offset for s in M.PARAM_SPECS]
-
-
-def head_rows(B: int) -> int:
-    """Batch rows per workgroup of the three-launch path's head kernel: 2 up to B=256 (more
-    workgroups on the otherwise idle chip, profiles/r2_v26_head_rows_groups_sweep.txt), 4 above
-    (each workgroup streams all of fc2)."""
-    return 2 if B <= 256 else 4
-
-
-# The engine's path choices (constructor ``variant=``).  None = chosen per configuration.
-VARIANT_DEFAULTS = {
-    "split_fwd": False,        # conv1 and conv2 forward as two launches (bitwise reference of conv12_fwd)
-    "fc_fused": None,          # the persistent fc chain (B <= 256, one rank per GPU); env DMLC_FC_FUSED=0 off
-    "fc_dgrad": None,          # conv2 dgrad inside the fc chain (default: on; two workgroups per image at B <= 128)
-    "fc_dw_in_wgrad": None,    # fc dW tiles in the wgrad launch (default: only when the dgrad is not in the chain)
-    "fc1_epilogue": True,      # single GPU: the fc1 update in the dW1 epilogue
-    "wgrad_sgd": True,         # in-launch SGD / slab reduction of the wgrad launch; env DMLC_WGRAD_SGD=0 off
-    "wgrad_sgd_fp8": False,    # the same for --dtype fp8 (bit-identical, measured 1.4 % slower at B=1024)
-    "fp8_dgrad": True,         # fp8: the conv2 input gradient on e4m3 too
-    "fp8_wgrad": True,         # fp8 (with fp8_dgrad): the conv2 weight gradient on e4m3 MFMA (per-batch scales)
-    "comm_sgd": False,         # data parallel over xGMI: the SGD in the exchange kernel's epilogue
-    "xraw_prefetch": True,     # the step's raw images gathered by the previous step's finalizer
-    "fwd12_split": True,       # B <= 128: conv1 + conv2 forward in one launch, two workgroups per image;
-                               # env DMLC_FWD12_SPLIT=0 off
-    "fc_sgd_in_chain": None,   # single GPU, dW tiles in the fc chain: every fc SGD in their epilogues (default B < 256)
-    "grad16": True,            # data parallel, RCCL, bf16 wire, fc chain: the producers write a bf16 flat gradient
-                               # (no cast launches around the all-reduce; bitwise the cast path)
-    "bwd_fused": None,         # single GPU, bf16, 128 < B <= 256: fc chain + conv2 dgrad + wgrad/SGD in one launch
-}
-# int32 words of the SGD arrival ticket (DMLC_TICKET_WORDS in csrc/kernels/api.h)
-TICKET_WORDS = 9 * 32
-# int32 words of the wgrad apply-mode barriers (DMLC_WBAR_WORDS); the last line is the error word
-WBAR_WORDS = 20 * 32
-# int32 words of the one-launch backward's per-image hand-off words (DMLC_HAND_WORDS)
-HAND_WORDS = 2 * 256 * 32
 # the engine attributes the dict-taking ops read by name (FusedCifarEngine.buf)
 BUF_NAMES = ("master", "grad", "grad16", "part1", "partb1", "part2", "partb2", "w1f", "w2f", "w2d", "fc1n", "fc2t",
              "fc2n", "fc3t", "fc3d", "step_t", "step_sgd", "ticket", "loss_part", "correct_part", "stats", "bidx",
@@ -145,36 +115,57 @@ class FusedCifarEngine:
                  dp_schedule: str = "serial", dp_force: bool = False, warmup_steps: int = 0,
                  conv_split: Optional[int] = None, conv1_split: Optional[int] = None,
                  dgrad_split: Optional[int] = None, variant: Optional[dict] = None):
-        unknown = set(variant or {}) - set(VARIANT_DEFAULTS)
-        if unknown:
-            raise ValueError(f"unknown engine variant keys {sorted(unknown)}")
-        V = dict(VARIANT_DEFAULTS, **(variant or {}))
-        self.variant = V
-        ops = _ops()
-        self.ops = ops
+        self.ops = _ops()
         self.device = torch.device(device or "cuda")
         dev = self.device
-        Bv = int(batch_size)
-        if Bv < 1:
-            raise ValueError("batch size must be >= 1")
-        B = -(-Bv // 16) * 16              # kernel batch: padded to the 16-row MFMA tile
-        self.B, self.Bv = B, Bv
         self.world_size, self.rank, self.pg = world_size, rank, process_group
-        # dp_force: run the data-parallel step (all-reduce + apply) even at world_size 1 -- exercises
-        # the collective path (e.g. a captured RCCL all-reduce) on a single GPU
-        self.dp = world_size > 1 or dp_force
         self.lr0, self.decay, self.decay_steps, self.staircase = lr, lr_decay, decay_steps, staircase
         self.warmup = float(warmup_steps)      # linear LR warm-up (large-batch recipe), in the SGD kernel
         self.relu_logits = relu_logits
         self.cy, self.cx = crop_offset
         self.comm_dtype = comm_dtype
-        if capture_comm is None:     # RCCL collectives go into the step graph unless told otherwise
-            capture_comm = self.dp and self._pg_backend() == "nccl"
-        self.capture_comm = bool(capture_comm)
         self.seed = seed
-        if dtype not in ("bf16", "fp8"):
-            raise ValueError("fused engine dtype must be bf16 or fp8")
         self.dtype = dtype
+
+        # --- the planner's inputs: everything read from the process, the device and the fabric -------
+        on_gpu = dev.type == "cuda"
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count if on_gpu else 0
+        ndev = torch.cuda.device_count() if on_gpu else 0
+        local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world_size))
+        dp = world_size > 1 or dp_force          # (StepPlan.dp)
+        if capture_comm is None:     # RCCL collectives go into the step graph unless told otherwise
+            capture_comm = dp and self._pg_backend() == "nccl"
+        self.capture_comm = bool(capture_comm)
+        if flat_params is None:
+            flat_params = M.init_flat_params(torch.Generator().manual_seed(seed))
+        n_flat = flat_params.numel()
+        # gradient all-reduce: xGMI peer-to-peer kernel over an IPC-shared grad buffer when every
+        # rank can map every peer and it measures faster than RCCL (parallel/xgmi.py), else RCCL
+        self.xgmi, self.comm_info = None, {"allreduce": "rccl" if dp else "none"}
+        self._buckets = {True: (M.FC_BUCKET_OFFSET, n_flat - M.FC_BUCKET_OFFSET), False: (0, M.FC_BUCKET_OFFSET)}
+        if world_size > 1 and on_gpu and comm_dtype in ("fp32", "bf16") and allreduce != "rccl":
+            from ..parallel import xgmi as X
+            # timed on the call pattern the step will issue: one whole-buffer all-reduce (serial) or
+            # the fc bucket then the conv bucket (overlap)
+            pattern = ([(0, n_flat)] if dp_schedule == "serial" else [self._buckets[True], self._buckets[False]])
+            self.xgmi, self.comm_info = X.select(n_flat, rank, world_size, dev, pattern, mode=allreduce,
+                                                 group=process_group, wire=comm_dtype, captured=self.capture_comm)
+        elif dp_force and world_size == 1 and allreduce == "xgmi" and on_gpu:
+            # a one-rank xGMI context (no peers): the DP step's exchange kernel on a single GPU
+            from ..parallel import xgmi as X
+            self.xgmi = X.XgmiAllReduce(n_flat, 0, 1, None, wire=comm_dtype)
+            self.comm_info = {"allreduce": "xgmi", "wire": comm_dtype}
+        self.plan_inputs = dict(batch_size=batch_size, dtype=dtype, world_size=world_size, dp_force=dp_force,
+                                local_world=local_world, ndev=ndev, cus=cus, have_xgmi=self.xgmi is not None,
+                                comm_dtype=comm_dtype, conv_split=conv_split, conv1_split=conv1_split,
+                                dgrad_split=dgrad_split, g1=g1, g2=g2, fc1_split=fc1_split, variant=variant)
+
+        # --- every path decision (engine/plan.py), then as plain attributes: tests flip some ----------
+        self.plan = plan_step(**self.plan_inputs)
+        for f in dataclasses.fields(self.plan):
+            setattr(self, f.name, getattr(self.plan, f.name))
+        B, Bv = self.B, self.Bv
+        self.keep_dp1 = False          # tests: also write the pool1 gradient to global memory
 
         # --- data (device resident) ---------------------------------------------------------
         assert data.dtype == torch.uint8 and tuple(data.shape[1:]) == (32, 32, 3)
@@ -192,28 +183,7 @@ class FusedCifarEngine:
         self.xraw = torch.zeros(B, 3072, dtype=torch.uint8, device=dev)
 
         # --- parameters + shadows -------------------------------------------------------------
-        if flat_params is None:
-            flat_params = M.init_flat_params(torch.Generator().manual_seed(seed))
         self.master = flat_params.to(dev, torch.float32).contiguous().clone()
-        # gradient all-reduce: xGMI peer-to-peer kernel over an IPC-shared grad buffer when every
-        # rank can map every peer and it measures faster than RCCL (parallel/xgmi.py), else RCCL
-        self.xgmi, self.comm_info = None, {"allreduce": "rccl" if self.dp else "none"}
-        self._buckets = {True: (M.FC_BUCKET_OFFSET, self.master.numel() - M.FC_BUCKET_OFFSET),
-                         False: (0, M.FC_BUCKET_OFFSET)}
-        if world_size > 1 and dev.type == "cuda" and comm_dtype in ("fp32", "bf16") and allreduce != "rccl":
-            from ..parallel import xgmi as X
-            # timed on the call pattern the step will issue: one whole-buffer all-reduce (serial) or
-            # the fc bucket then the conv bucket (overlap)
-            pattern = ([(0, self.master.numel())] if dp_schedule == "serial"
-                       else [self._buckets[True], self._buckets[False]])
-            self.xgmi, self.comm_info = X.select(self.master.numel(), rank, world_size, dev, pattern,
-                                                 mode=allreduce, group=process_group, wire=comm_dtype,
-                                                 captured=self.capture_comm)
-        elif dp_force and world_size == 1 and allreduce == "xgmi" and dev.type == "cuda":
-            # a one-rank xGMI context (no peers): the DP step's exchange kernel on a single GPU
-            from ..parallel import xgmi as X
-            self.xgmi = X.XgmiAllReduce(self.master.numel(), 0, 1, None, wire=comm_dtype)
-            self.comm_info = {"allreduce": "xgmi", "wire": comm_dtype}
         if self.xgmi is not None:
             self.grad = self.xgmi.buf[:self.master.numel()]
             self.grad.zero_()
@@ -225,56 +195,20 @@ class FusedCifarEngine:
         # fc1's bf16 shadow is double-buffered by step parity ([2][2304][384]): the kernels of step s
         # read fc1n[s & 1] and the update writes fc1n[(s + 1) & 1], so at N=1 the dW1 GEMM can apply
         # the fc1 update in its epilogue while the dp2 problem of the same launch still reads the
-        # current weights (fc1_epilogue below)
+        # current weights (fc1_epilogue)
         self.fc1n, self.fc2t, self.fc2n = z(2, 2304, 384), z(192, 384), z(384, 192)
         self.fc3t, self.fc3d = z(16, 192), z(192, 32)
-        # fp8 conv2 forward + input gradient (BASELINE config 5): e4m3 weight shadows [0] forward
-        # (co-major) and [1] the dgrad's flipped ci-major copy, delayed per-tensor weight scale;
-        # variant fp8_dgrad=False keeps the conv2 input gradient in bf16
-        self.fp8 = dtype == "fp8"
-        self.fp8_dgrad = self.fp8 and bool(V["fp8_dgrad"])
-        if self.fp8:
+        if self.fp8:         # e4m3 conv2 weight shadows ([0] forward, [1] the dgrad's) + their scales
             self.w2f8 = z(2, 64, 1600, dt=torch.uint8)
             self.amax_x = z(B, dt=torch.float32)      # per-image activation maxima (conv1 -> conv2)
             self.amax_w = z(2, 400, dt=torch.float32)  # [slot][SGD conv2-row block] weight maxima
             self.scale_w = z(2, dt=torch.float32)
-        # fp8 conv2 weight gradient (cnn_wgrad.hip w2_fp8_main): the e4m3 X the fp8 forward quantised
-        # (per-batch scale sx) and the e4m3 dY2 the fp8 dgrad quantised (a power-of-two scale per
-        # image, the MFMA's E8M0 block scale), written by those kernels next to their bf16 outputs
-        self.fp8_wgrad = self.fp8_dgrad and bool(V["fp8_wgrad"])
-        if self.fp8_wgrad:
+        if self.fp8_wgrad:   # the e4m3 X / dY2 of the fp8 conv2 weight gradient and their scales
             self.p1f8, self.dy2f8 = z(B, 144, 64, dt=torch.uint8), z(B, 144, 64, dt=torch.uint8)
             self.sx8, self.sy_img = z(1, dt=torch.float32), torch.ones(B, dtype=torch.float32, device=dev)
         self._w8 = dict(fp8=[self.p1f8, self.dy2f8, self.sx8, self.sy_img]) if self.fp8_wgrad else {}
 
         # --- activations / workspaces -------------------------------------------------------
-        self.fc1_split = fc1_split or self._pick_fc1_split(B)
-        # conv1 and conv2 forward in one launch (bf16 path; variant split_fwd: two launches)
-        self.fused_fwd = not V["split_fwd"]
-        # channel-split convolutions (cnn_split.hip): conv_split = 2 runs conv1 forward (conv1_split =
-        # 2 or 4 workgroups per image), conv2 forward and the conv2 input gradient as 2 workgroups per
-        # image, so a small batch fills the 256 CUs; 1 = one workgroup per image (cnn_conv.hip).
-        # same-session A/B (r3): B=128 73.5 us (split, conv1 2-way) vs 74.6 (conv1 4-way) vs 79.0 (one
-        # workgroup per image); B=256 85.1 vs 82.9 -- the split pays only while the chip is not full
-        self.conv_split = 1 if self.fp8 else (conv_split or (2 if B <= 128 else 1))
-        self.conv1_split = conv1_split or 2
-        # the conv2 input gradient's split, independently of the forward's
-        self.dgrad_split = 1 if self.fp8 else (dgrad_split or self.conv_split)
-        if self.conv_split not in (1, 2) or self.conv1_split not in (2, 4) or self.dgrad_split not in (1, 2):
-            raise ValueError(f"conv_split / dgrad_split must be 1 or 2 and conv1_split 2 or 4 "
-                             f"({self.conv_split}, {self.dgrad_split}, {self.conv1_split})")
-        self.keep_dp1 = False          # tests: also write the pool1 gradient to global memory
-        # Both weight gradients run in ONE launch (ops.wgrad) of g1 + 4 * g2 <= 256 blocks (one wave
-        # of workgroups): conv2 one block per (input-channel quarter, image group), one fp32 slab per
-        # group (g2 = slabs the reduction sums); conv1 one block per image group on the CUs the conv2
-        # blocks leave.  Multiples of 8 keep every group's images on one XCD (cnn_wgrad.hip).
-        # B=128: 32 groups of 4 images -> 69.2 us per step vs 16 groups of 8 -> 73.7 (r3 sweep);
-        # B=256: 32 -> 81.7 vs 24 -> 85.1, 40 -> 83.1, 48 -> 86.8.  Past B=256 every conv1 block takes
-        # several images instead of the grid growing beyond the chip.
-        g2_ = max(1, min(B, 32, B // 4))
-        self.g2 = g2 or (g2_ // 8 * 8 if g2_ >= 8 else g2_)
-        self.g1 = g1 or max(1, min(B, 256 - 4 * self.g2))
-        self.groups2 = self.g2
         self.p1, self.am1 = z(B, 12, 12, 64), z(B, 12, 12, 64, dt=torch.uint8)
         self.p2, self.am2 = z(B, 6, 6, 64), z(B, 6, 6, 64, dt=torch.uint8)
         self.h1part = z(self.fc1_split, B, 384, dt=torch.float32)
@@ -287,23 +221,11 @@ class FusedCifarEngine:
         # to the conv2 weight gradient and a 7 % drift in the loss-curve parity test: not kept.)
         self.part2, self.partb2 = z(self.g2, 1600, 64, dt=torch.float32), z(self.g2, 64, dt=torch.float32)
         self.part1, self.partb1 = z(self.g1, 80, 64, dt=torch.float32), z(self.g1, 64, dt=torch.float32)
-        # the whole fc chain of a training step (fc1 forward, head, fc backward) as ONE persistent
-        # launch (cnn_fc.hip) instead of three: B <= 256, 256 co-resident workgroups (one per CU, so
-        # not when several ranks share a GPU).  DMLC_FC_FUSED=0 turns it off.
-        local_ = int(os.environ.get("LOCAL_WORLD_SIZE", world_size))
-        ndev_ = torch.cuda.device_count() if dev.type == "cuda" else 0
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 0
-        fc_ok = B <= 256 and cus >= 256 and local_ <= max(1, ndev_)
-        self.fc_fused = (fc_ok if V["fc_fused"] is None else bool(V["fc_fused"]) and fc_ok) \
-            and os.environ.get("DMLC_FC_FUSED", "1") != "0"
-        self.h1part8 = z(8, B, 384, dt=torch.float32) if self.fc_fused else None
-        self.fc_sync = torch.zeros(212 * 32, dtype=torch.int32, device=dev)   # fc_common.h SY_END
+        self.h1part8 = z(8, B, 384, dt=torch.float32) if self.has_h1part8 else None
+        self.fc_sync = torch.zeros(FC_SYNC_WORDS, dtype=torch.int32, device=dev)
         self._fc_src = None
-        # head: head_rows(B) batch rows per workgroup (B / rows workgroups share the fc2 weight reads);
-        # the fused fc chain's head takes 4 rows per workgroup
-        hr = 4 if self.fc_fused else head_rows(B)
-        self.loss_part = z(B // hr, dt=torch.float32)
-        self.correct_part = z(B // hr, dt=torch.int32)
+        self.loss_part = z(self.loss_parts, dt=torch.float32)
+        self.correct_part = z(self.loss_parts, dt=torch.int32)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
         # the head kernel copies the step counter here; the SGD (launch or in-launch) reads the copy,
         # so one of its workgroups can bump step_t without an arrival ticket (cnn_sgd.hip)
@@ -316,16 +238,9 @@ class FusedCifarEngine:
         self.pv = p
         gv = {k: self.grad[s.offset:s.offset + s.numel] for k, s in SEG.items()}
         self.gv = gv
-        # data parallel over RCCL with the bf16 wire: the fc chain (its dW tiles), the wgrad launch's
-        # conv-slab reduction / the reduce-only SGD launch write the gradient as bf16 into grad16, the
-        # all-reduce runs on it in place and the apply-only SGD reads it (DmlcSgdArgs::grad16) -- the
-        # fp32 gradient + t.to(bf16) + all-reduce + copy back, bit for bit, minus two cast launches of
-        # 4.27 / 2.1 MB (world-1 A/B: +13.1 us over the single-GPU step with the casts vs +5.7 fp32,
-        # profiles/r6s2_dp1_ab_grad16_bf16.jsonl).  The three-launch fc path writes fp32 only: fc chain
-        # engines (B <= 256, a GPU per rank) only.
-        self.grad16 = None
-        if (self.dp and comm_dtype == "bf16" and self.xgmi is None and self.fc_fused and bool(V["grad16"])):
-            self.grad16 = torch.zeros(self.master.numel(), dtype=torch.bfloat16, device=dev)
+        # the bf16 flat gradient of the RCCL bf16 wire (has_grad16)
+        self.grad16 = (torch.zeros(self.master.numel(), dtype=torch.bfloat16, device=dev) if self.has_grad16
+                       else None)
 
         # grouped GEMM problem lists (the three-launch fc path)
         self._fc1_fwd = dict(A=[self.p2.view(B, 2304)], B=[self.fc1n], C=[self.h1part], bias=[None],
@@ -345,116 +260,19 @@ class FusedCifarEngine:
                     + _gemm_params(192, 8, B, 192, 0, 8, 0, 1, 3, nvalid=192)      # db2
                     + _gemm_params(16, 8, B, 16, 0, 8, 0, 1, 3, nvalid=10)))       # db3
         fb = self._fc_bwd
-        # single GPU: the same launch with dW1 as a fused SGD epilogue (c_mode 4) -- the fc1 weights
-        # (83 % of the parameters) are updated where their gradient is produced instead of the fp32
-        # gradient going through HBM to the SGD kernel (which then updates the fc1 bias only).
-        # Bitwise the same update (same lr expression, same fp32 arithmetic); variant fc1_epilogue off
-        self.fc1_epilogue = not self.dp and bool(V["fc1_epilogue"])
-        # single GPU + fc1 epilogue: the merged weight-gradient launch also runs the rest of the SGD
-        # (cnn_wgrad.hip apply mode: sub-grid barriers per slab family, the SGD kernel's reduction
-        # order -> bit-identical weights) and the step has no SGD launch.  DMLC_WGRAD_SGD=0 off.
-        in_launch = (1 <= self.g1 <= cus and 4 * self.g2 <= cus and bool(V["wgrad_sgd"])
-                     and os.environ.get("DMLC_WGRAD_SGD", "1") != "0")
-        # fp8: bit-identical too (the e4m3 shadows + amax slots in-launch), but measured slower at
-        # B=1024 (207.5 vs 204.7 us, profiles/r3_fp8_wgrad_sgd_ab.txt): variant wgrad_sgd_fp8 opts in
-        self.wgrad_apply = in_launch and self.fc1_epilogue and (not self.fp8 or bool(V["wgrad_sgd_fp8"]))
-        # data parallel: the same launch reduces the conv slabs into the flat gradient (the reduce-only
-        # SGD launch before the all-reduce goes away).  Needs the launch's blocks co-resident, so not
-        # when several ranks share one GPU (rehearsals / tests: another rank's kernels hold CUs).
-        local = int(os.environ.get("LOCAL_WORLD_SIZE", world_size))
-        ndev = torch.cuda.device_count() if dev.type == "cuda" else 0
-        reduce_ok = in_launch and self.dp and local <= max(1, ndev)
-        # reduce-only also serves compute_gradients() on one GPU (fp8 included: bit for bit the
-        # two-launch path, tests/test_fp8_gpu.py)
-        self._grad_in_launch = in_launch and (self.wgrad_apply or reduce_ok)
-        # the data-parallel step takes the in-launch reduction exactly when compute_gradients() does
-        # (one predicate: the DP step and _conv_backward can never disagree)
-        self.wgrad_reduce = self.dp and self._grad_in_launch
-        # data parallel over xGMI, serial schedule, variant comm_sgd: the exchange kernel applies the
-        # SGD in its epilogue (k_xgmi_allreduce_sgd: no SGD launch; bit-identical weights; bf16 shadows
-        # only).  Off by default: measured on one GPU (tools/dp1_ab.py, world-1 xGMI context, B=256)
-        # the DP step took 103.0 us with the epilogue on the exchange's 128 workgroups and 142.2 us on
-        # 512 (every workgroup pays the barriers' system-scope release fences) vs 96.2 us for exchange
-        # + the 800-workgroup SGD launch (profiles/r5_dp1_ab_128blocks.jsonl, r5_dp1_ab_512blocks.jsonl).
-        self.comm_sgd = self.xgmi is not None and not self.fp8 and bool(V["comm_sgd"])
-        # workgroups of the exchange + SGD kernel: 2 per CU on a GPU of its own (the epilogue streams
-        # the whole flat buffer); ranks sharing one GPU (rehearsals) split the workgroups, since every
-        # workgroup waits at the barriers for the same-index workgroup of every peer
-        share = max(1, -(-int(os.environ.get("LOCAL_WORLD_SIZE", world_size)) // max(1, ndev)))
-        self._comm_blocks = 512 if share == 1 else max(32, 128 // share)
-        # the training forward (conv12_fwd) reads its raw images from xraw, which the previous step's
-        # finalizer (wgrad apply mode, the SGD launch or the xGMI+SGD kernel) filled with the next
-        # step's rows -- one image load instead of index load -> image load at the head of the step;
-        # the host fills it whenever it sets the step (_sync_bidx)
-        self.xraw_prefetch = self.fused_fwd and not self.fp8 and self.conv_split == 1 and bool(V["xraw_prefetch"])
-        # B <= 128 (channel-split convs, conv1 in halves): conv1 -> conv2 in ONE launch whose two
-        # workgroups per image swap their pool1 halves through sc1 stores + a flag (cnn_split.hip
-        # k_conv12_fwd_split) -- one launch boundary and the conv2 input's global round trip less
-        self.fwd12_split = (self.conv_split == 2 and self.conv1_split == 2 and not self.fp8
-                            and B * 2 <= cus and local_ <= max(1, ndev_) and bool(V["fwd12_split"])
-                            and os.environ.get("DMLC_FWD12_SPLIT", "1") != "0")
-        self.c12_flags = torch.zeros(32 * 2 * B if self.fwd12_split else 1, dtype=torch.int32, device=dev)
-        self.wbar = torch.zeros(WBAR_WORDS, dtype=torch.int32, device=dev)   # barrier words + error word
-        # pinned host copy of the barrier error word, refreshed by queue_error_copy() behind each
-        # chunk of steps (the trainer checks it at every progress point without a device sync)
-        self._err_host = (torch.zeros(1, dtype=torch.int32).pin_memory() if dev.type == "cuda"
-                          else torch.zeros(1, dtype=torch.int32))
-        # the plain bf16 conv2 dgrad (one image per workgroup) runs in the fc chain's workgroups, each
-        # once its dp2 row tile is published: one launch boundary less, but the hand-off (publish ->
-        # poll -> sc1 dp2 loads) costs ~2 us of it back.  With the fc dW tiles kept in the chain (below)
-        # it measured 1.8-2.5 us/step faster at B = 144 / 160 / 192 / 224 / 256 (profiles/
-        # r4_v8_fc_dgrad_b144_256_ab.txt); at B <= 128 the chain's 256 workgroups run the split dgrad
-        # (two per image, cnn_split.hip's halves) instead of its own launch (r5, profiles/
-        # r5_fc_split_dgrad_b128_ab.txt).  Variant fc_dgrad forces it on / off.
-        fdg = V["fc_dgrad"]
-        self.fc_dgrad = self.fc_fused and not self.fp8_dgrad and (bool(fdg) if fdg is not None else True)
-        self._dgrad_done = False
-        # single GPU, fused fc chain + apply mode: the fc weight-gradient tiles and every fc SGD can run
-        # in the wgrad launch's conv1 blocks (between their barrier arrival and the conv1 reduction),
-        # so the fc chain launch ends with its dp2 tiles.  Same-box A/B at B=256 (profiles/
-        # r4_v7_fc_dgrad_dw_ab.txt, us/step): chain dgrad off: dW in chain 81.8, in wgrad 80.4; chain
-        # dgrad on: dW in chain 79.8, in wgrad 80.2 -- so by default the dW tiles move to the wgrad
-        # launch only when the dgrad is not in the chain.  Variant fc_dw_in_wgrad forces it.
-        # At B <= 128 (the chain's split dgrad) the dW tiles once measured better in the wgrad launch
-        # (64.2-64.4 vs 65.6-65.9 us at B = 128, profiles/r5_fc_split_dgrad_b128_ab.txt) -- with the
-        # conv1 blocks then too busy to help reduce the conv2 slabs.  With the tiles in the chain the
-        # conv1 blocks help again (torch_ops.cpp: helpers whenever they carry no fc tiles): B = 32 71.6
-        # -> 64.0, 64 65.3 -> 62.7, 96 65.8 -> 64.7, 112 67.5 -> 65.5, 128 63.6 -> 63.6 us
-        # (profiles/r5_dw_placement_helpers_ab.txt).
-        fdw = V["fc_dw_in_wgrad"]
-        self.fc_dw_in_wgrad = (self.fc_fused and self.wgrad_apply
-                               and (bool(fdw) if fdw is not None else not self.fc_dgrad))
-        # ... and with the tiles in the chain, the chain can apply every fc SGD in their epilogues (fc2 /
-        # fc3 / fc biases too, as the wgrad launch does when it runs them): the wgrad launch's conv1
-        # blocks then have no fc SGD roles before their conv1 reduction and conv2 help, while the
-        # chain's dW2 / dW3 tiles (whose images' dgrads end the chain) carry the transposed-shadow
-        # epilogues.  Same-box A/B (profiles/r5_fc_sgd_in_chain_ab.txt): B = 64 / 128 / 160 / 192 / 224
-        # -0.9 / -0.3 / -0.5 / -0.9 / -0.7 us, B = 256 +0.9 us -- on below B = 256.
-        fsc = V["fc_sgd_in_chain"]
-        self.fc_sgd_in_chain = (self.fc_fused and self.wgrad_apply and not self.fc_dw_in_wgrad
-                                and (bool(fsc) if fsc is not None else B < 256))
-        # the whole backward -- fc chain, conv2 dgrad, both weight gradients and the SGD -- in ONE launch
-        # (cnn_bwd.hip k_backward): the chain's and the wgrad launch's 256 workgroups are the same 256, so
-        # each block starts its weight-gradient role the moment its own dgrad is done and waits per image
-        # instead of per launch, and the blocks that finish the chain first take the conv2 roles, which
-        # end the step.  Bitwise the two launches (tests/test_bwd_fused_gpu.py).  Where: the chain with
-        # its one-workgroup-per-image dgrad and its dW tiles, the wgrad launch in apply mode on the
-        # full 256-block grid, bf16 state, one rank.  The fc SGD roles of the wgrad launch would read
-        # the chain's flat gradient inside the launch, so this path has the chain apply every fc SGD in
-        # its dW epilogues (fc_sgd_in_chain, also at B = 256) and is off when that variant is forced off.
-        bwf = V["bwd_fused"]
-        bwd_ok = (self.fc_fused and self.fc_dgrad and 128 < B <= 256 and self.dgrad_split == 1
-                  and self.wgrad_apply and not self.fc_dw_in_wgrad and not self.fp8 and world_size == 1
-                  and self.xraw_prefetch and fsc is not False and self.g1 + 4 * self.g2 == 256
-                  and self.g1 % 8 == 0 and self.g2 % 8 == 0)
-        self.bwd_fused = bool(bwd_ok and (bool(bwf) if bwf is not None else True))
-        if self.bwd_fused:
-            self.fc_sgd_in_chain = True
-        self.bwd_hand = torch.zeros(HAND_WORDS if self.bwd_fused else 1, dtype=torch.int32, device=dev)
+        # single GPU (fc1_epilogue): the same launch with dW1 as a fused SGD epilogue (c_mode 4)
         self._fc_bwd_sgd = dict(fb, C=[fb["C"][0], p["full_weight_1"]] + fb["C"][2:],
                                 params=fb["params"][:14] + _gemm_params(2304, 384, B, 2304, 0, 384, 0, 384, 4,
                                                                         s_par=FC1_NUMEL)
                                 + fb["params"][28:])
+        self.c12_flags = torch.zeros(self.c12_flags_words, dtype=torch.int32, device=dev)
+        self.wbar = torch.zeros(WBAR_WORDS, dtype=torch.int32, device=dev)   # barrier words + error word
+        # pinned host copy of the barrier error word, refreshed by queue_error_copy() behind each
+        # chunk of steps (the trainer checks it at every progress point without a device sync)
+        self._err_host = (torch.zeros(1, dtype=torch.int32).pin_memory() if on_gpu
+                          else torch.zeros(1, dtype=torch.int32))
+        self._dgrad_done = False
+        self.bwd_hand = torch.zeros(self.bwd_hand_words, dtype=torch.int32, device=dev)
 
         self.graphs: List[torch.cuda.CUDAGraph] = []
         self.chains: Dict[int, Optional[torch.cuda.CUDAGraph]] = {}   # k -> graph of k chained steps
@@ -480,18 +298,6 @@ class FusedCifarEngine:
         self.refresh_shadows()
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _pick_fc1_split(B: int) -> int:
-        # the largest power-of-two split in (8, 4, 2) whose (B/64) * 6 tiles * split workgroups stay
-        # <= 450: with the XCD-aware GEMM order (cnn_gemm.hip) every XCD gets its own K slice of p2
-        # and W1 (split 8: one slice per XCD).  Whole-step sweeps: tools/sweep_fc.py,
-        # profiles/r2_v26_fc1_split_sweep.jsonl.
-        tiles = max(1, math.ceil(B / 64)) * 6
-        for s in (8, 4, 2):
-            if tiles * s <= 450:
-                return s
-        return 1
-
     def refresh_shadows(self):
         if self.fp8:    # exact amax of the current W2 for the shadow quantisation at this step
             s = self.host_step & 1
@@ -542,7 +348,7 @@ class FusedCifarEngine:
         if self.fwd12_split:                       # one launch, two workgroups per image (cnn_split.hip)
             o.conv12_fwd(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
                          self.am1, self.w2f, p["conv2_bias"], self.p2, self.am2, self.xraw if train else None, False,
-                         self.c12_flags, self.wbar[10 * 32:10 * 32 + 1])
+                         self.c12_flags, self.wbar[ERR_WORD:ERR_WORD + 1])
         elif self.conv_split == 2 and not self.fp8:  # channel-split: B * nsplit workgroups per conv
             o.conv1_fwd_split(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
                               self.am1, self.xraw if train else None, self.conv1_split)
@@ -662,7 +468,7 @@ class FusedCifarEngine:
         """Enqueue a copy of the barrier error word into pinned host memory (stream-ordered: valid once
         an event recorded after this call has completed)."""
         if self.barriers_in_use:
-            self._err_host.copy_(self.wbar[10 * 32:10 * 32 + 1], non_blocking=True)
+            self._err_host.copy_(self.wbar[ERR_WORD:ERR_WORD + 1], non_blocking=True)
 
     def check_barriers(self, cached: bool = False):
         """Raise if a sub-grid barrier of the wgrad launch timed out (sticky device error word): apply
@@ -671,7 +477,7 @@ class FusedCifarEngine:
         it.  ``cached``: read the pinned copy of :meth:`queue_error_copy` (no device sync)."""
         if not self.barriers_in_use:
             return
-        e = int(self._err_host[0]) if cached else int(self.wbar[10 * 32].item())
+        e = int(self._err_host[0]) if cached else int(self.wbar[ERR_WORD].item())
         if e != 0:
             # error word: value 1 = a wgrad sub-grid barrier, value 2 = an fc chain hand-off timed out
             mode = "apply" if self.wgrad_apply else "reduce"
@@ -1045,7 +851,7 @@ class FusedCifarEngine:
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.pg)
             # a persistent launch's bounded wait timed out on some rank: that schedule is out (the
             # sticky word is cleared for the run that follows; every rank sees the same MAX)
-            e = torch.tensor([int(self.wbar[10 * 32].item()) if self.barriers_in_use else 0],
+            e = torch.tensor([int(self.wbar[ERR_WORD].item()) if self.barriers_in_use else 0],
                              dtype=torch.float64, device=bdev)
             dist.all_reduce(e, op=dist.ReduceOp.MAX, group=self.pg)
             if self.xgmi is not None:
@@ -1053,7 +859,7 @@ class FusedCifarEngine:
             if float(e.item()) != 0.0:
                 if log:
                     log(f"dp schedule {sched}: a persistent launch's wait timed out -- not eligible")
-                self.wbar[10 * 32].zero_()
+                self.wbar[ERR_WORD].zero_()
                 times[sched].append(math.inf)
                 continue
             times[sched].append(float(t.item()) / iters)

@@ -539,6 +539,26 @@ def test_xraw_prefetch_is_bit_identical(B):
         assert pre.read_stats(s) == ref.read_stats(s), s
 
 
+def test_engine_runs_exactly_its_plan():
+    """The engine takes the paths engine/plan.py chose from the inputs it collected: every plan field
+    is the engine attribute of the same name, planning again from ``plan_inputs`` gives the same plan,
+    and a step on those paths leaves no barrier error.  B = 16 / 144: the smallest batches on the
+    split forward and on the one-launch backward."""
+    import dataclasses
+    from dmlc.engine.plan import plan_step
+    for B in (16, 144):
+        data, labels = _synthetic(2 * B, seed=5)
+        eng = FusedCifarEngine(B, data, labels, seed=6, lr=1e-4, relu_logits=False)
+        assert (eng.fwd12_split, eng.bwd_fused) == (B == 16, B == 144)
+        for f in dataclasses.fields(eng.plan):
+            assert getattr(eng, f.name) == getattr(eng.plan, f.name), (B, f.name)
+        assert plan_step(**eng.plan_inputs) == eng.plan
+        eng.step()
+        torch.cuda.synchronize()
+        eng.check_barriers()
+        assert eng.global_step() == 1 and torch.isfinite(eng.master).all()
+
+
 _SPIN0 = "spin0:-DDMLC_SPIN_LIMIT=0"
 _SPIN0_SCRIPT = r"""
 import json, sys, torch
