@@ -24,10 +24,18 @@ uint8_t* xraw_ptr(const c10::optional<Tensor>& xraw, int64_t B) {
   return xraw->data_ptr<uint8_t>();
 }
 
+// optional int32 [B] per-image augmentation words (api.h DmlcConv1FwdArgs::aug), by batch row
+const int* aug_ptr(const c10::optional<Tensor>& aug, int64_t B) {
+  if (!aug.has_value()) return nullptr;
+  check_numel(*aug, "aug", at::kInt, B);
+  return aug->data_ptr<int>();
+}
+
 
 void conv1_fwd(const Tensor& data, const Tensor& idx, const c10::optional<Tensor>& counter, int64_t period,
                int64_t cy, int64_t cx, const Tensor& w1f, const Tensor& b1, const Tensor& out, const Tensor& am,
-               const c10::optional<Tensor>& amax, const c10::optional<Tensor>& xraw) {
+               const c10::optional<Tensor>& amax, const c10::optional<Tensor>& xraw,
+               const c10::optional<Tensor>& aug) {
   const int64_t B = out.size(0);
   check_data(data);
   TORCH_CHECK(cy >= 0 && cy <= 8 && cx >= 0 && cx <= 8, "crop offsets must be in [0,8]");
@@ -46,6 +54,7 @@ void conv1_fwd(const Tensor& data, const Tensor& idx, const c10::optional<Tensor
   a.amax = nullptr;
   a.xraw = xraw_ptr(xraw, B);
   a.xraw_in = 0;
+  a.aug = aug_ptr(aug, B);
   if (amax.has_value()) {
     check_numel(*amax, "amax", at::kFloat, B);
     a.amax = amax->data_ptr<float>();
@@ -95,7 +104,7 @@ void conv12_fwd(const Tensor& data, const Tensor& idx, const c10::optional<Tenso
                 int64_t cy, int64_t cx, const Tensor& w1f, const Tensor& b1, const Tensor& p1, const Tensor& am1,
                 const Tensor& w2f, const Tensor& b2, const Tensor& p2, const Tensor& am2,
                 const c10::optional<Tensor>& xraw, bool xraw_in, const c10::optional<Tensor>& split_flags,
-                const c10::optional<Tensor>& err) {
+                const c10::optional<Tensor>& err, const c10::optional<Tensor>& aug) {
   const int64_t B = p1.size(0);
   TORCH_CHECK(!xraw_in || xraw.has_value(), "conv12_fwd: xraw_in needs the prefetched images");
   const bool split = split_flags.has_value();
@@ -120,6 +129,7 @@ void conv12_fwd(const Tensor& data, const Tensor& idx, const c10::optional<Tenso
   a1.amax = nullptr;
   a1.xraw = xraw_ptr(xraw, B);
   a1.xraw_in = xraw_in ? 1 : 0;
+  a1.aug = aug_ptr(aug, B);
   DmlcConv2FwdArgs a2;
   a2.in = p1.data_ptr(); a2.w = w2f.data_ptr(); a2.bias = b2.data_ptr<float>();
   a2.out = p2.data_ptr(); a2.am = am2.data_ptr<uint8_t>(); a2.B = (int)B;
@@ -165,7 +175,7 @@ void conv2_dgrad(const Tensor& dp2, const Tensor& am2, const Tensor& w2d, const 
 // conv2_dgrad; the kernel batch must be a multiple of 8 (the engine pads it to 16)
 void conv1_fwd_split(const Tensor& data, const Tensor& idx, const c10::optional<Tensor>& counter, int64_t period,
                      int64_t cy, int64_t cx, const Tensor& w1f, const Tensor& b1, const Tensor& out, const Tensor& am,
-                     const c10::optional<Tensor>& xraw, int64_t nsplit) {
+                     const c10::optional<Tensor>& xraw, int64_t nsplit, const c10::optional<Tensor>& aug) {
   const int64_t B = out.size(0);
   TORCH_CHECK(B % 8 == 0, "split kernels need a batch multiple of 8");
   TORCH_CHECK(nsplit == 2 || nsplit == 4, "conv1 split must be 2 or 4");
@@ -186,6 +196,7 @@ void conv1_fwd_split(const Tensor& data, const Tensor& idx, const c10::optional<
   a.amax = nullptr;
   a.xraw = xraw_ptr(xraw, B);
   a.xraw_in = 0;
+  a.aug = aug_ptr(aug, B);
   CHECK_HIP(dmlc_conv1_fwd_split(&a, (int)nsplit, stream_of(out)));
 }
 
@@ -248,7 +259,8 @@ static DmlcWgradArgs make_wgrad(const Tensor& data, const Tensor& idx, const c10
                                 const Tensor& part1, const Tensor& partb1, const Tensor& p1, const Tensor& dy2,
                                 const Tensor& part2, const Tensor& partb2, int64_t groups2,
                                 const c10::optional<Tensor>& xraw,
-                                const c10::optional<at::TensorList>& fp8 = c10::nullopt) {
+                                const c10::optional<at::TensorList>& fp8 = c10::nullopt,
+                                const c10::optional<Tensor>& aug = c10::nullopt) {
   const int64_t B = p1.size(0), g1 = part1.size(0), g2 = groups2;
   check_data(data);
   TORCH_CHECK(cy >= 0 && cy <= 8 && cx >= 0 && cx <= 8, "crop offsets must be in [0,8]");
@@ -271,6 +283,7 @@ static DmlcWgradArgs make_wgrad(const Tensor& data, const Tensor& idx, const c10
   a.w1.dp1 = dp1.data_ptr(); a.w1.am1 = am1.data_ptr<uint8_t>();
   a.w1.part1 = part1.data_ptr<float>(); a.w1.partb1 = partb1.data_ptr<float>(); a.w1.g1 = (int)g1; a.w1.B = (int)B;
   a.w1.xraw = xraw_ptr(xraw, B);
+  a.w1.aug = aug_ptr(aug, B);
   a.w2.p1 = p1.data_ptr(); a.w2.dy2 = dy2.data_ptr(); a.w2.part2 = part2.data_ptr();
   a.w2.partb2 = partb2.data_ptr<float>(); a.w2.g2 = (int)g2; a.w2.B = (int)B;
   if (fp8.has_value()) {
@@ -292,9 +305,10 @@ static DmlcWgradArgs make_wgrad(const Tensor& data, const Tensor& idx, const c10
 void wgrad(const Tensor& data, const Tensor& idx, const c10::optional<Tensor>& counter, int64_t period, int64_t cy,
            int64_t cx, const Tensor& dp1, const Tensor& am1, const Tensor& part1, const Tensor& partb1,
            const Tensor& p1, const Tensor& dy2, const Tensor& part2, const Tensor& partb2, int64_t groups2,
-           const c10::optional<Tensor>& xraw, const c10::optional<at::TensorList> fp8) {
+           const c10::optional<Tensor>& xraw, const c10::optional<at::TensorList> fp8,
+           const c10::optional<Tensor>& aug) {
   DmlcWgradArgs a = make_wgrad(data, idx, counter, period, cy, cx, dp1, am1, part1, partb1, p1, dy2, part2, partb2,
-                               groups2, xraw, fp8);
+                               groups2, xraw, fp8, aug);
   c10::DeviceGuard guard(dp1.device());
   CHECK_HIP(dmlc_wgrad(&a, stream_of(dp1)));
 }
@@ -659,6 +673,10 @@ DmlcSgdArgs make_sgd(const Tensor& master, const Buf& buf, at::IntArrayRef off, 
     TORCH_CHECK(a.next.idx_base == nullptr, "sgd: order must be the host descriptor");
     a.bidx = bidx.data_ptr<int>(); a.bidx_n = (int)bidx.numel();
   }
+  if (has(buf, "aug")) {                   // the next step's augmentation words, written with bidx
+    TORCH_CHECK(a.bidx, "sgd: the augmentation table needs bidx");
+    a.aug = need_numel(buf, "aug", at::kInt, a.bidx_n).data_ptr<int>();
+  }
   if (prefetch) {
     TORCH_CHECK(a.bidx, "sgd: prefetching the next images needs the dataset and bidx");
     const Tensor xdata = need(buf, "data");
@@ -707,7 +725,8 @@ DmlcWgradArgs make_wgrad_sgd(const Tensor& master, const Buf& buf, const Tensor&
   DmlcWgradArgs a = make_wgrad(need(buf, "data"), idx, counter, period, cy, cx, need(buf, "dp1"), need(buf, "am1"),
                                need(buf, "part1"), need(buf, "partb1"), need(buf, "p1"), need(buf, "dy2"),
                                need(buf, "part2"), need(buf, "partb2"), groups2, need(buf, "xraw"),
-                               fp8 ? c10::optional<at::TensorList>(*fp8) : c10::nullopt);
+                               fp8 ? c10::optional<at::TensorList>(*fp8) : c10::nullopt,
+                               has(buf, "aug") ? c10::optional<Tensor>(need(buf, "aug")) : c10::nullopt);
   a.sgd = make_sgd(master, buf, off, sched, order, mode, 0, true, mode == 0, batch, prefetch);
   TORCH_CHECK(mode != 0 || sched[5] == 1.0, "wgrad_sgd: the single-GPU step takes no gradient scale");
   a.apply = 1;
@@ -778,24 +797,25 @@ void backward_fused(const Tensor& master, const Buf& buf, const Tensor& idx, con
 
 TORCH_LIBRARY(dmlc, m) {
   m.def("conv1_fwd(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor w1f, Tensor b1, "
-        "Tensor(a!) out, Tensor(b!) am, Tensor(c!)? amax=None, Tensor(d!)? xraw=None) -> ()");
+        "Tensor(a!) out, Tensor(b!) am, Tensor(c!)? amax=None, Tensor(d!)? xraw=None, Tensor? aug=None) -> ()");
   m.def("conv2_fwd_fp8(Tensor inp, Tensor w8, Tensor b2, Tensor amax_x, Tensor scale_w, Tensor? counter, "
         "Tensor(a!) out, Tensor(b!) am, Tensor(c!)? x8out=None, Tensor(d!)? sx_out=None) -> ()");
   m.def("fp8_roundtrip(Tensor x, Tensor(a!) y, float scale) -> ()");
   m.def("conv2_fwd(Tensor inp, Tensor w2f, Tensor b2, Tensor(a!) out, Tensor(b!) am) -> ()");
   m.def("conv12_fwd(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor w1f, Tensor b1, "
         "Tensor(a!) p1, Tensor(b!) am1, Tensor w2f, Tensor b2, Tensor(c!) p2, Tensor(d!) am2, "
-        "Tensor(e!)? xraw=None, bool xraw_in=False, Tensor(f!)? split_flags=None, Tensor(g!)? err=None) -> ()");
+        "Tensor(e!)? xraw=None, bool xraw_in=False, Tensor(f!)? split_flags=None, Tensor(g!)? err=None, "
+        "Tensor? aug=None) -> ()");
   m.def("conv2_dgrad(Tensor dp2, Tensor am2, Tensor w2d, Tensor(a!) dp1, Tensor(b!) dy2) -> ()");
   m.def("conv1_fwd_split(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor w1f, Tensor b1, "
-        "Tensor(a!) out, Tensor(b!) am, Tensor(c!)? xraw, int nsplit) -> ()");
+        "Tensor(a!) out, Tensor(b!) am, Tensor(c!)? xraw, int nsplit, Tensor? aug=None) -> ()");
   m.def("conv2_fwd_split(Tensor inp, Tensor w2f, Tensor b2, Tensor(a!) out, Tensor(b!) am) -> ()");
   m.def("conv2_dgrad_split(Tensor dp2, Tensor am2, Tensor w2d, Tensor(a!) dp1, Tensor(b!) dy2) -> ()");
   m.def("conv2_dgrad_fp8(Tensor dp2, Tensor am2, Tensor w2d8, Tensor scale_w, Tensor(a!) dp1, Tensor(b!) dy2, "
         "Tensor(c!)? dy8out=None, Tensor(d!)? sy_img=None) -> ()");
   m.def("wgrad(Tensor data, Tensor idx, Tensor? counter, int period, int cy, int cx, Tensor dp1, Tensor am1, "
         "Tensor(a!) part1, Tensor(b!) partb1, Tensor p1, Tensor dy2, Tensor(c!) part2, Tensor(d!) partb2, "
-        "int groups2, Tensor? xraw=None, Tensor[]? fp8=None) -> ()");
+        "int groups2, Tensor? xraw=None, Tensor[]? fp8=None, Tensor? aug=None) -> ()");
   m.def("gemm_grouped(Tensor[] A, Tensor[] B, Tensor(a!)[] C, Tensor?[] bias, int[] params, Tensor? step=None, "
         "Tensor(b!)? shadow=None, float[] sched=[]) -> ()");
   m.def("head(Tensor h1part, Tensor b1, Tensor w2t, Tensor b2, Tensor w3t, Tensor b3, Tensor w3d, Tensor w2d, "

@@ -47,7 +47,21 @@ struct DmlcConv1FwdArgs {
   uint8_t* xraw;            // nullable: copy of each row's raw uint8 image [B][3072] for the wgrad
   int xraw_in;              // k_conv12_fwd: read row b's image from xraw[b] (written for this step by
                             //   the previous step's finalizer), no index load, no copy-out
+  const int* aug;           // nullable: per-image augmentation words [B] by batch row (see below);
+                            //   null = the launch-wide cy, cx with no flip
 };
+
+// Per-image random crop + horizontal flip (augmentation).  Word of batch row b:
+//   cy | cx << 4 | flip << 8   (cy, cx in 0..8),   x_aug[y][x][c] = img[cy + y][flip ? cx + 23 - x : cx + x][c]
+// a pure function of (shuffle seed, global step, row in the union batch of all ranks): common.h
+// aug_word, host twin dmlc/data/order.py.  The table is ONE int32 [B] buffer, not double-buffered:
+// the host writes the current step's words (engine _sync_bidx) and the launch that finalizes step s
+// writes the words of step s + 1 (DmlcSgdArgs::aug).  In the weight-gradient launch's apply mode the
+// conv1 blocks read this step's words in the launch that rewrites them, so that write sits BEHIND the
+// conv1 family's barrier, which every conv1 block passes only after its image loop (its last reader);
+// the SGD launch and the xGMI epilogue run after the weight-gradient launch and have no such hazard.
+// xraw always holds the RAW image rows, with or without aug: crop and flip are applied where the
+// image is expanded (forward: conv_common.h stage_conv1_input; backward: w1_common.h w1_planes).
 
 // conv2 5x5 (64->64) + bias + ReLU + maxpool 3x3/2 TF-SAME.  One workgroup per image.
 struct DmlcConv2FwdArgs {
@@ -108,6 +122,7 @@ struct DmlcConv1WgradArgs {
   DmlcIndexSrc src;
   const uint8_t* xraw;      // nullable: the forward's copy [B][3072] (row b) instead of data[src(b)]
   int cy, cx;
+  const int* aug;           // nullable: augmentation words [B] (DmlcConv1FwdArgs::aug), else cy, cx, no flip
   const void* dp1;          // bf16 [B][12][12][64]  grad wrt pool1 output
   const uint8_t* am1;       // [B][12][12][64]
   float* part1;             // [g1][80][64]  k'' = kh*16 + kw*3 + ci (k'' % 16 == 15 unused)
@@ -265,6 +280,9 @@ struct DmlcSgdArgs {
   // evaluating the Feistel order themselves (~150 scalar instructions per row per wave).
   int* bidx; int bidx_n;
   DmlcIndexSrc next;
+  // nullable (needs bidx): the finalizing launch also writes aug[b] = the augmentation word of batch
+  // row b at step+1 (seed, rank, bvalid of `next`); see DmlcConv1FwdArgs for the in-launch hazard
+  int* aug;
   // fc1n is [2][2304][384] (step-parity double buffer: kernels of step s read fc1n[s & 1]); modes
   // 0/2 write fc1n[(s+1) & 1], mode 3 fc1n[s & 1].  fc1_fused (mode 0): the fc1 WEIGHT update already
   // ran in the dW1 GEMM's epilogue (c_mode 4) -- the fc1 role covers the fc1 bias only

@@ -71,8 +71,7 @@ __global__ __launch_bounds__(NT, 1) void k_conv1_fwd(DmlcConv1FwdArgs a) {
   const int img = batch_index(a.src, a.B, b);
   uint8_t* raw = reinterpret_cast<uint8_t*>(cout) + 16;     // the conv output region is free until the epilogue
   stage_conv1_raw(raw, a.data + (size_t)img * 3072, a.xraw ? a.xraw + (size_t)b * 3072 : nullptr, tid);
-  __syncthreads();
-  stage_conv1_input(xin, raw, a.cy, a.cx, tid);
+  stage_conv1_crop<false>(xin, raw, a, b, tid);
 
   // A operand: weights [64 co][96 k]; this wave owns co tiles 2cp, 2cp+1 (32 channels) and the
   // pixel tiles 9pq .. 9pq+8 (of 36): every B fragment read from LDS feeds two MFMAs.
@@ -201,8 +200,7 @@ __global__ __launch_bounds__(NT, 1) void k_conv12_fwd(DmlcConv1FwdArgs a1, DmlcC
     const int img = batch_index(a1.src, a1.B, b);
     stage_conv1_raw(raw, a1.data + (size_t)img * 3072, a1.xraw ? a1.xraw + (size_t)b * 3072 : nullptr, tid);
   }
-  lds_barrier();   // (the xraw copy's global stores need not drain)
-  stage_conv1_input(xin, raw, a1.cy, a1.cx, tid);
+  stage_conv1_crop<true>(xin, raw, a1, b, tid);   // (LDS-only barrier: the xraw copy's global stores need not drain)
   // conv2's padded input: zero halo (rows/cols 0,1,14,15); the interior comes from pool1
   for (int s = tid; s < 2048; s += NT) {
     const int pix = s >> 3, c = s & 7, r = pix >> 4, col = pix & 15;

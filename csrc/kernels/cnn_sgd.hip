@@ -110,7 +110,10 @@ __global__ __launch_bounds__(256) void k_sgd(DmlcSgdArgs a) {
   // the next step's batch rows (no kernel of this step reads bidx any more: they all ran before)
   if (a.bidx && (int)blockIdx.x * 256 < a.bidx_n) {
     const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r < a.bidx_n) a.bidx[r] = order_row(a.next, step + 1, r);
+    if (r < a.bidx_n) {
+      a.bidx[r] = order_row(a.next, step + 1, r);
+      if (a.aug) a.aug[r] = aug_row(a.next, step + 1, r);   // (as bidx: every reader ran before)
+    }
   }
   // ... and their raw images (the wgrad launch, the last reader of xnext, has completed)
   if (a.xnext)

@@ -79,8 +79,7 @@ DEV void conv1_split_body(const DmlcConv1FwdArgs& a, int b, int h, bf16* xin, bf
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
     for (int i = 0; i < 4; ++i) b4[ct][i] = a.bias[co0 + 16 * ct + 4 * g + i];
-  __syncthreads();
-  stage_conv1_input(xin, raw, a.cy, a.cx, tid);
+  stage_conv1_crop<false>(xin, raw, a, b, tid);
   __syncthreads();
   DMLC_STAMP(DMLC_TK_CONV1_FWD, 1);
 

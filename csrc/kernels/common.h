@@ -362,6 +362,32 @@ DEV int order_row(const Src& s, int64_t step, int b) {
   return (int)order_perm(pos, (uint32_t)s.n, s.half_bits, s.seed, epoch);
 }
 
+// Augmentation word of row g of the step's union batch (all ranks): cy | cx << 4 | flip << 8 with the
+// crop offsets cy, cx in 0..8 -- a keyed pure function like the order, no RNG state.  Host twin:
+// dmlc/data/order.py (aug_words).
+DEV int aug_word(uint32_t seed, int64_t step, uint32_t g) {
+  const uint32_t k = mix32(mix32(seed ^ 0xa0761d65u) ^ mix32((uint32_t)step * 0x9e3779b1u + 0x7f4a7c15u));
+  const uint32_t h = mix32(k ^ (g * 0x85ebca77u + 0xc2b2ae3du));
+  const uint32_t cy = ((h & 0xffffu) * 9u) >> 16, cx = (((h >> 16) & 0x7fffu) * 9u) >> 15;
+  return (int)(cy | cx << 4 | (h >> 31) << 8);
+}
+// ... of batch row b of this rank at `step` (padding rows b >= bvalid carry the last valid row's word)
+template <class Src>
+DEV int aug_row(const Src& s, int64_t step, int b) {
+  const int bb = b < s.bvalid ? b : s.bvalid - 1;
+  return aug_word(s.seed, step, (uint32_t)(s.rank * s.bvalid + bb));
+}
+
+// The crop of one image from its augmentation word (read at a wave-uniform index: one scalar load,
+// and cy / cx / flip live in SGPRs).  The offsets are clamped to the image so that a corrupt table
+// cannot address outside it.
+struct Crop { int cy, cx, flip; };
+DEV Crop crop_decode(int word) {
+  const int w = __builtin_amdgcn_readfirstlane(word);
+  Crop c = {min(w & 15, 8), min((w >> 4) & 15, 8), (w >> 8) & 1};
+  return c;
+}
+
 // Sample index of batch row b (api.h DmlcIndexSrc: explicit list or generated epoch order).
 template <class Src>
 DEV int batch_index(const Src& s, int B, int b) {

@@ -125,6 +125,52 @@ DEV void stage_conv1_input(bf16* xin, const uint8_t* raw, int cy, int cx, int ti
   }
 }
 
+// The horizontally flipped crop (augmentation): output column x shows crop column 23 - x, so the
+// window's pixels x + kw - 2 run DOWN the raw row while each pixel's channels still run up.  Element
+// j = kw*3 + ci is byte 3 * (4 - kw) + ci of the 15 bytes starting at crop column 21 - x (the pixel
+// of kw = 4): a fixed byte permutation per window half, read as single bytes (the flipped windows are
+// the slower path; the unflipped one above is untouched).  Reads stay inside raw's 8-byte slack.
+DEV void stage_conv1_input_flip(bf16* xin, const uint8_t* raw, int cy, int cx, int tid) {
+  const int h = tid & 1;
+  int pos[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int j = 8 * h + e, kw = j / 3;
+    pos[e] = j < 15 ? 3 * (4 - kw) + (j - 3 * kw) : 0;
+  }
+  for (int t = tid; t < 28 * 24 * 2; t += NT) {
+    const int px = t >> 1, r = px / 24, x = px - r * 24, iy = r - 2;
+    const bool rok = iy >= 0 && iy < 24;
+    const uint8_t* win = raw + (rok ? ((cy + iy) * 32 + cx + 21 - x) * 3 : 8);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int j = 8 * h + e, ix = x + j / 3 - 2;
+      const float v = (float)win[pos[e]];
+      f[e] = rok && j < 15 && ix >= 0 && ix < 24 ? v : 0.f;
+    }
+    *reinterpret_cast<bf16x8*>(xin + px * 16 + 8 * h) = to_bf16x8(f);
+  }
+}
+
+// The barrier that publishes raw (stage_conv1_raw), then image b's expansion: by its augmentation word
+// (a.aug set), else at the launch-wide crop.  The table's presence is a launch-wide branch taken
+// BEFORE the barrier, so that without a table the code on both sides of the barrier is exactly the
+// launch-wide crop's (its loop set-up overlaps the image load's latency in front of the barrier).
+// LDS_ONLY: lds_barrier instead of __syncthreads.
+template <bool LDS_ONLY>
+DEV void stage_conv1_crop(bf16* xin, const uint8_t* raw, const DmlcConv1FwdArgs& a, int b, int tid) {
+  if (a.aug) {
+    const Crop c = crop_decode(a.aug[b]);
+    if constexpr (LDS_ONLY) lds_barrier(); else __syncthreads();
+    if (c.flip) stage_conv1_input_flip(xin, raw, c.cy, c.cx, tid);   // wave-uniform
+    else stage_conv1_input(xin, raw, c.cy, c.cx, tid);
+  } else {
+    if constexpr (LDS_ONLY) lds_barrier(); else __syncthreads();
+    stage_conv1_input(xin, raw, a.cy, a.cx, tid);
+  }
+}
+
 // conv1 B fragments of pixel px (lane li of its tile): k-step s, lane group g holds k = 32s + 8g ..
 // +7 = kernel row 2s + (g >> 1), window half g & 1; the pad rows k >= 80 (s = 2, g >= 2) re-read
 // row 4 against zero weights.

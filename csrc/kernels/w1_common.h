@@ -39,6 +39,8 @@ DEV void w1_ones_plane15(bf16* xs, int tid) {
 
 // (a) shifted channel planes straight from the uint8 image in LDS: task (yy, x8, kw) -> planes
 //     kw*3+{0,1,2}, 8 pixels: plane[kw*3+ci][yy][x] = crop[ci][yy-2][x+kw-2] (0 outside the crop)
+//     FLIP (augmentation): crop column ix is raw column cx + 23 - ix; img holds the raw rows either way
+template <bool FLIP>
 DEV void w1_planes(bf16* xs, const uint8_t* img, int cy, int cx, int tid) {
   for (int task = tid; task < 28 * 3 * 5; task += W1T) {
     const int kw = task % 5, r = task / 5, x8 = r % 3, yy = r / 3, iy = yy - 2;
@@ -49,7 +51,7 @@ DEV void w1_planes(bf16* xs, const uint8_t* img, int cy, int cx, int tid) {
     for (int j = 0; j < 8; ++j) {
       const int ix = x8 * 8 + kw + j - 2;
       const bool ok = rok && ix >= 0 && ix < 24;
-      const uint8_t* px = srow + (ok ? ix : 0) * 3;
+      const uint8_t* px = srow + (ok ? (FLIP ? 23 - ix : ix) : 0) * 3;
       const float f0 = px[0], f1 = px[1], f2 = px[2];
       o0[j] = (bf16)(ok ? f0 : 0.f); o1[j] = (bf16)(ok ? f1 : 0.f); o2[j] = (bf16)(ok ? f2 : 0.f);
     }
@@ -58,6 +60,11 @@ DEV void w1_planes(bf16* xs, const uint8_t* img, int cy, int cx, int tid) {
     *reinterpret_cast<bf16x8*>(dst + W1_PL) = o1;
     *reinterpret_cast<bf16x8*>(dst + 2 * W1_PL) = o2;
   }
+}
+
+DEV void w1_planes(bf16* xs, const uint8_t* img, const Crop& c, int tid) {
+  if (c.flip) w1_planes<true>(xs, img, c.cy, c.cx, tid);   // wave-uniform
+  else w1_planes<false>(xs, img, c.cy, c.cx, tid);
 }
 
 // (b) pool1 / ReLU backward -> dY1 (bf16, LDS) as a SCATTER: every pool1 window adds its gradient

@@ -97,6 +97,9 @@ DEV void conv1_wgrad_block(const DmlcConv1WgradArgs& a, const int grp, char* sme
   };
   // with the forward's image copy (xraw) no dataset index is needed at all
   auto row_index = [&](int bb) { return a.xraw ? 0 : batch_index(a.src, a.B, bb); };
+  // the image's augmentation word, read one image ahead like the dataset row.  Without a table
+  // (a.aug null, a launch-wide branch) the loop below is the launch-wide crop's code, barrier included.
+  int nword = a.aug ? a.aug[b0 < last ? b0 : last] : 0;
   if constexpr (INL) {
     // the first image: everything the hand-off does not gate goes out, then one lane waits for its
     // dP1 word (the only wait that can be exposed: later images' waits sit under an image's compute)
@@ -123,10 +126,20 @@ DEV void conv1_wgrad_block(const DmlcConv1WgradArgs& a, const int grp, char* sme
     w1_zero_dy(dyt, tid);
     load(nidx, b + G < last ? b + G : last);   // prefetch the next image while this one computes
     nidx = row_index(b + 2 * G < last ? b + 2 * G : last);
-    lds_barrier();
-    if (b == b0) DMLC_STAMP(DMLC_TK_W1, 1);
-    if (b == b0 + G) DMLC_STAMP(DMLC_TK_W1, 6);
-    w1_planes(xs, img, a.cy, a.cx, tid);
+    auto staged = [&]() __attribute__((always_inline)) {
+      lds_barrier();
+      if (b == b0) DMLC_STAMP(DMLC_TK_W1, 1);
+      if (b == b0 + G) DMLC_STAMP(DMLC_TK_W1, 6);
+    };
+    if (a.aug) {
+      const Crop crop = crop_decode(nword);
+      nword = a.aug[b + G < last ? b + G : last];
+      staged();
+      w1_planes(xs, img, crop, tid);
+    } else {
+      staged();
+      w1_planes<false>(xs, img, a.cy, a.cx, tid);
+    }
     w1_pool_bwd(dyt, dps, ams, w, lane);       // ends with a barrier: dY1 and the planes complete
     if (b == b0) DMLC_STAMP(DMLC_TK_W1, 2);
     if (b == b0 + G) DMLC_STAMP(DMLC_TK_W1, 7);
@@ -736,6 +749,12 @@ DEV void conv1_apply(const DmlcWgradArgs& A, int grp, char* smem, unsigned g0, i
   __syncthreads();
   DMLC_STAMP(DMLC_TK_SGD, 1);
   if constexpr (INL) finish_step();
+  // the next step's augmentation words: the conv1 blocks of THIS launch read this step's words in
+  // their image loops, and the complete barrier above proves every one of them is past its loop
+  if (s.mode == 0 && s.bidx && s.aug) {
+    const int r = grp * W1T + tid;
+    if (r < s.bidx_n) s.aug[r] = aug_row(s.next, step + 1, r);
+  }
   const int per = (1200 + n - 1) / n, ol = tid & 15, sp = tid >> 4;
   const rsrc_t part1 = buf_rsrc(A.w1.part1);
   for (int f0 = 0; f0 < per; f0 += 16) {

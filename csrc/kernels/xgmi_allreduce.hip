@@ -226,7 +226,10 @@ __global__ __launch_bounds__(XT) void k_xgmi_allreduce_sgd(XgmiArgs a, DmlcSgdAr
 #endif
   const float lr = lr_of(S, step);
   for (int64_t i = a.off4 + t0; i < a.off4 + a.n4; i += stride) sgd_apply4(S, i, lr, step);
-  if (S.bidx && t0 < S.bidx_n) S.bidx[t0] = order_row(S.next, step + 1, (int)t0);
+  if (S.bidx && t0 < S.bidx_n) {
+    S.bidx[t0] = order_row(S.next, step + 1, (int)t0);
+    if (S.aug) S.aug[t0] = aug_row(S.next, step + 1, (int)t0);
+  }
   if (S.xnext)
     for (int r = blockIdx.x; r < S.bidx_n; r += gridDim.x) copy_next_row(S, step, r, threadIdx.x);
   if (blockIdx.x == 0 && threadIdx.x < 64) publish_step(S, step, lr, threadIdx.x);

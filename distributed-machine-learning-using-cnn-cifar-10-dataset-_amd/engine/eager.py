@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from .. import config as C
-from ..data.order import OrderSpec
+from ..data.order import OrderSpec, apply_augment, unpack_aug
 from ..models import build_model
 
 
@@ -78,19 +78,24 @@ class EagerTrainer:
             self.cur_epoch = epoch
         row = step % self.period
         idx = self.perm[row * self.B:(row + 1) * self.B]
-        return self.images(idx), self.labels[idx]
+        return self.images(idx, step), self.labels[idx]
 
-    def images(self, idx: torch.Tensor) -> torch.Tensor:
+    def images(self, idx: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
+        """The cropped float images of dataset rows ``idx``.  With augmentation and a ``step``: the
+        per-image random crop + flip of that step's batch rows (D5), from the same keyed words as the
+        fused kernels (data/order.py ``OrderSpec.augment``) -- reproducible, and equal on every engine
+        and on the union batch of all ranks.  The 24x24 crop takes the word's offsets; any other crop
+        size stays centred and takes the word's flip only."""
         o, c = self.off, self.crop
         x = self.data[idx]
-        if self.augment:
-            # random crop (±off) + horizontal flip, per batch (optional, D5)
-            dy, dx = (int(v) for v in torch.randint(0, 2 * o + 1, (2,)))
-            x = x[:, dy:dy + c, dx:dx + c, :]
-            if torch.rand(()) < 0.5:
-                x = x.flip(2)
-        else:
+        if self.augment and step is not None:
+            words = self.order.augment(step)[:x.shape[0]]
+            if c == 24:
+                return apply_augment(x, words).float()
             x = x[:, o:o + c, o:o + c, :]
+            flip = unpack_aug(words)[2].to(x.device).view(-1, 1, 1, 1) == 1
+            return torch.where(flip, x.flip(2), x).float()
+        x = x[:, o:o + c, o:o + c, :]
         return x.float()
 
     def _allreduce_grads(self):

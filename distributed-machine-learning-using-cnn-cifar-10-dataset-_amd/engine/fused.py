@@ -88,7 +88,7 @@ BUF_NAMES = ("master", "grad", "grad16", "part1", "partb1", "part2", "partb2", "
              "fc2n", "fc3t", "fc3d", "step_t", "step_sgd", "ticket", "loss_part", "correct_part", "stats", "bidx",
              "xraw", "data", "labels", "p1", "p2", "am1", "am2", "dp1", "dp2", "dy2", "h1part8", "h1", "h2", "dl",
              "dh1", "dh2", "fc_sync", "wbar", "bwd_hand", "w2f8", "amax_w", "scale_w", "p1f8", "dy2f8", "sx8",
-             "sy_img")
+             "sy_img", "aug")
 SEG = {M.short(s.name): s for s in M.PARAM_SPECS}
 
 
@@ -114,7 +114,7 @@ class FusedCifarEngine:
                  capture_comm: Optional[bool] = None, dtype: str = "bf16", allreduce: str = "auto",
                  dp_schedule: str = "serial", dp_force: bool = False, warmup_steps: int = 0,
                  conv_split: Optional[int] = None, conv1_split: Optional[int] = None,
-                 dgrad_split: Optional[int] = None, variant: Optional[dict] = None):
+                 dgrad_split: Optional[int] = None, variant: Optional[dict] = None, augment: bool = False):
         self.ops = _ops()
         self.device = torch.device(device or "cuda")
         dev = self.device
@@ -123,6 +123,11 @@ class FusedCifarEngine:
         self.warmup = float(warmup_steps)      # linear LR warm-up (large-batch recipe), in the SGD kernel
         self.relu_logits = relu_logits
         self.cy, self.cx = crop_offset
+        # per-image random crop + flip of the training batches (api.h DmlcConv1FwdArgs::aug); the
+        # evaluation forwards keep the constructor's crop
+        self.augment = bool(augment)
+        if self.augment and tuple(crop_offset) != (4, 4):
+            raise ValueError("augment needs the 24x24 crop: crop_offset must be (4, 4)")
         self.comm_dtype = comm_dtype
         self.seed = seed
         self.dtype = dtype
@@ -181,6 +186,9 @@ class FusedCifarEngine:
         self.bidx = torch.zeros(B, dtype=torch.int32, device=dev)
         # raw uint8 images of the step's rows, written by the forward for the conv1 weight gradient
         self.xraw = torch.zeros(B, 3072, dtype=torch.uint8, device=dev)
+        # this step's augmentation words by batch row (int32 [B]), kept like bidx: the finalizer of
+        # step s writes those of step s+1, the host writes them whenever it sets the step
+        self.aug = torch.zeros(B, dtype=torch.int32, device=dev) if self.augment else None
 
         # --- parameters + shadows -------------------------------------------------------------
         self.master = flat_params.to(dev, torch.float32).contiguous().clone()
@@ -317,6 +325,8 @@ class FusedCifarEngine:
 
     def _sync_bidx(self):
         self.bidx.copy_(self._padded(self.batch_indices(self.host_step)))
+        if self.aug is not None:
+            self.aug.copy_(self.order.augment(self.host_step, pad_to=self.B))
         self._sync_xraw()
 
     def _sync_xraw(self):
@@ -345,21 +355,23 @@ class FusedCifarEngine:
     # --- kernels ------------------------------------------------------------------------------
     def _forward(self, idx, counter, period, train=True, logits_out=None):
         o, p = self.ops, self.pv
+        aug = dict(aug=self.aug) if train and self.aug is not None else {}
         if self.fwd12_split:                       # one launch, two workgroups per image (cnn_split.hip)
             o.conv12_fwd(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
                          self.am1, self.w2f, p["conv2_bias"], self.p2, self.am2, self.xraw if train else None, False,
-                         self.c12_flags, self.wbar[ERR_WORD:ERR_WORD + 1])
+                         self.c12_flags, self.wbar[ERR_WORD:ERR_WORD + 1], **aug)
         elif self.conv_split == 2 and not self.fp8:  # channel-split: B * nsplit workgroups per conv
             o.conv1_fwd_split(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
-                              self.am1, self.xraw if train else None, self.conv1_split)
+                              self.am1, self.xraw if train else None, self.conv1_split, **aug)
             o.conv2_fwd_split(self.p1, self.w2f, p["conv2_bias"], self.p2, self.am2)
         elif self.fused_fwd and not self.fp8:      # conv1 + pool1 + conv2 + pool2 in one launch
             pre = train and self.xraw_prefetch and idx is self.bidx   # the step's own (prefetched) batch
             o.conv12_fwd(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
-                         self.am1, self.w2f, p["conv2_bias"], self.p2, self.am2, self.xraw if train else None, pre)
+                         self.am1, self.w2f, p["conv2_bias"], self.p2, self.am2, self.xraw if train else None, pre,
+                         **aug)
         else:
             o.conv1_fwd(self.data, idx, counter, period, self.cy, self.cx, self.w1f, p["conv1_bias"], self.p1,
-                        self.am1, self.amax_x if self.fp8 else None, self.xraw if train else None)
+                        self.am1, self.amax_x if self.fp8 else None, self.xraw if train else None, **aug)
         if self.fp8:
             o.conv2_fwd_fp8(self.p1, self.w2f8[0], p["conv2_bias"], self.amax_x, self.scale_w, counter, self.p2, self.am2,
                             *((self.p1f8, self.sx8) if train and self.fp8_wgrad else (None, None)))
@@ -442,7 +454,7 @@ class FusedCifarEngine:
             return
         o.wgrad(self.data, idx, counter, period, self.cy, self.cx, self.dp1, self.am1,
                 self.part1, self.partb1, self.p1, self.dy2, self.part2, self.partb2, self.groups2, self.xraw,
-                **self._w8)
+                **self._w8, **({"aug": self.aug} if self.aug is not None else {}))
 
     def _sched(self, scale: float = 1.0) -> list:
         """{lr0, decay, decay_steps, staircase, warmup, grad_scale} of the SGD ops and the fc chain."""

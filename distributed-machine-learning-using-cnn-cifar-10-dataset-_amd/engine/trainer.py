@@ -55,7 +55,8 @@ class _FusedAdapter:
                                     staircase=cfg.lr_schedule == "staircase", relu_logits=cfg.relu_logits,
                                     crop_offset=((32 - cfg.crop) // 2,) * 2, comm_dtype=cfg.comm_dtype,
                                     dtype=cfg.dtype, allreduce=cfg.allreduce,
-                                    dp_schedule="serial" if cfg.dp_schedule == "auto" else cfg.dp_schedule)
+                                    dp_schedule="serial" if cfg.dp_schedule == "auto" else cfg.dp_schedule,
+                                    augment=cfg.augment)
         self.cfg = cfg
         self.graph = cfg.graph
         from ..models import cifar_cnn as M
@@ -257,9 +258,9 @@ class _EagerAdapter:
 def pick_impl(cfg: C.TrainConfig, device: torch.device) -> str:
     if cfg.impl != "auto":
         return cfg.impl
-    if (device.type == "cuda" and cfg.model == "cifar_cnn" and cfg.dtype in ("bf16", "fp8") and cfg.crop == 24
-            and not cfg.augment):
-        return "fused"                    # any batch size: masked tail rows (engine/fused.py)
+    if device.type == "cuda" and cfg.model == "cifar_cnn" and cfg.dtype in ("bf16", "fp8") and cfg.crop == 24:
+        # any batch size: masked tail rows; --augment: per-image crop + flip in the kernels (engine/fused.py)
+        return "fused"
     if device.type == "cuda" and cfg.model == "cifar_cnn" and cfg.dtype == "fp32":
         return "hipf32"                   # reference precision on the fp32 HIP kernels (ops/f32.py)
     if (device.type == "cuda" and cfg.model == "resnet20" and cfg.dtype == "bf16" and cfg.crop == 32
