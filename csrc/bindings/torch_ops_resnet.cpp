@@ -258,7 +258,8 @@ void rn_sgd(const Tensor& master, const c10::optional<Tensor>& grad, double grad
             at::TensorList wd, const Tensor& stat, const Tensor& red, const Tensor& fc_part, const Tensor& loss_img,
             const Tensor& correct_img, const Tensor& step, const Tensor& ticket, const Tensor& stats, int64_t mode,
             double lr0, double decay, double decay_steps, bool staircase, double bn_momentum, double warmup,
-            int64_t layer_lo, int64_t layer_hi, bool tail, int64_t nvalid, const c10::optional<Tensor>& step_rd) {
+            int64_t layer_lo, int64_t layer_hi, bool tail, int64_t nvalid, const c10::optional<Tensor>& step_rd,
+            const c10::optional<Tensor>& vel, double momentum, double weight_decay) {
   constexpr int L = DMLC_RN_LAYERS;
   TORCH_CHECK(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi <= L, "rn_sgd: bad layer range");
   TORCH_CHECK(tail || mode == 0, "rn_sgd: a partial (tail=False) launch is mode 0 only");
@@ -285,9 +286,18 @@ void rn_sgd(const Tensor& master, const c10::optional<Tensor>& grad, double grad
     TORCH_CHECK(grad.has_value(), "rn_sgd modes 1/2 need grad");
     check_numel(*grad, "grad", at::kFloat, np);
   }
+  TORCH_CHECK(momentum >= 0.0 && momentum < 1.0, "rn_sgd: momentum must be in [0, 1)");
+  TORCH_CHECK(weight_decay >= 0.0, "rn_sgd: weight_decay must be >= 0");
+  if (vel.has_value()) {
+    check_numel(*vel, "vel", at::kFloat, np);
+    TORCH_CHECK(vel->device() == master.device(), "rn_sgd: vel must be on master's device");
+  }
+  TORCH_CHECK(vel.has_value() || momentum == 0.0 || (mode != 0 && mode != 2), "rn_sgd: momentum needs vel");
   DmlcRnSgdArgs a{};
   a.master = master.data_ptr<float>(); a.nparams = (int)np;
   a.grad = grad.has_value() ? grad->data_ptr<float>() : nullptr; a.grad_scale = (float)grad_scale;
+  a.vel = vel.has_value() ? vel->data_ptr<float>() : nullptr;
+  a.momentum = (float)momentum; a.weight_decay = (float)weight_decay;
   for (int l = 0; l < L; ++l) {
     const Geom g = geom(kLayers[l][0], kLayers[l][1], kLayers[l][2], kLayers[l][3]);
     TORCH_CHECK(conv_off[l] >= 0 && conv_off[l] % 4 == 0 && conv_off[l] + 9 * g.cin * g.cout <= np, "bad conv offset ", l);
@@ -358,7 +368,8 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
         "Tensor(d!)[] wf, Tensor(e!)[] wd, Tensor stat, Tensor red, Tensor fc_part, Tensor loss_img, "
         "Tensor correct_img, Tensor(f!) step, Tensor(g!) ticket, Tensor(h!) stats, int mode, float lr0, "
         "float decay, float decay_steps, bool staircase, float bn_momentum, float warmup=0.0, int layer_lo=0, "
-        "int layer_hi=19, bool tail=True, int nvalid=0, Tensor? step_rd=None) -> ()");
+        "int layer_hi=19, bool tail=True, int nvalid=0, Tensor? step_rd=None, Tensor(i!)? vel=None, "
+        "float momentum=0.0, float weight_decay=0.0) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {

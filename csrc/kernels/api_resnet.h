@@ -80,6 +80,11 @@ struct DmlcRnHeadArgs {
 struct DmlcRnSgdArgs {
   float* master; int nparams;
   float* grad; float grad_scale;   // DP: modes 1 (write) / 2 (read, scaled)
+  // momentum / L2 weight decay of the applying modes (0, 2): v <- momentum * v + (g + wd_eff * w),
+  // w <- w - lr * v; wd_eff = weight_decay for the conv kernels and the fc weight matrix, 0 for
+  // the fc bias and BN gamma / beta.  vel: nullable fp32 [nparams] in the layout of master
+  // (required when momentum != 0).  vel == nullptr and weight_decay == 0: plain w -= lr * g
+  float* vel; float momentum, weight_decay;
   // per conv layer
   int conv_off[DMLC_RN_LAYERS], gamma_off[DMLC_RN_LAYERS], beta_off[DMLC_RN_LAYERS];
   int cin[DMLC_RN_LAYERS], cout[DMLC_RN_LAYERS];

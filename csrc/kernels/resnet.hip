@@ -1126,6 +1126,17 @@ DEV float4 split_reduce(const float* p, size_t stride, int n, int S, float4* lds
   return t;
 }
 
+// The parameter update of every applying site (conv, fc, BN gamma / beta).  plain (no velocity
+// buffer, no weight decay): w - lr * g, the expression this kernel always had.  Otherwise
+// v <- mu * v + (g + wd * w), w <- w - lr * v with the rounding pinned by explicit fmaf, so modes 0
+// and 2 and every site round alike (g is materialised by the caller; wd = 0 for rank-1 parameters;
+// without a velocity buffer mu is 0 and v comes in as 0)
+DEV float sgd_update(float w, float g, float lr, float wd, float mu, float& v, bool plain) {
+  if (plain) return w - lr * g;
+  v = fmaf(mu, v, fmaf(wd, w, g));
+  return fmaf(-lr, v, w);
+}
+
 // modes: 0 reduce slabs + apply (1 GPU); 1 reduce slabs into `grad` (DP, before the all-reduce);
 //        2 apply grad_scale * `grad` (DP, after it); 3 refresh the bf16 shadows from the master only
 // blocks: [conv layer 0..18 | fc | BN layer 0..18]
@@ -1137,6 +1148,8 @@ __global__ __launch_bounds__(RT) void k_rn_sgd(DmlcRnSgdArgs a) {
   const float lr = a.warmup > 0.f && (float)step < a.warmup ? lr0 * ((float)step + 1.f) / a.warmup : lr0;
   const int mode = a.mode;
   const bool reduce = mode <= 1, apply = mode == 0 || mode == 2;
+  const float mu = a.momentum, wdec = a.weight_decay;
+  const bool plain = a.vel == nullptr && wdec == 0.f;     // the update without momentum / decay
   const int blk = blockIdx.x, tid = threadIdx.x;
   constexpr int NL = DMLC_RN_LAYERS;
   // (the BN blocks dispatched first instead of last measured no better: 612.0-612.9 vs 608.4-611.3
@@ -1170,8 +1183,14 @@ __global__ __launch_bounds__(RT) void k_rn_sgd(DmlcRnSgdArgs a) {
         float* m = a.master + off;
         float4 wv = *reinterpret_cast<float4*>(m);
         if (apply) {
-          wv.x -= lr * gsum.x; wv.y -= lr * gsum.y; wv.z -= lr * gsum.z; wv.w -= lr * gsum.w;
+          float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (a.vel) vv = *reinterpret_cast<const float4*>(a.vel + off);
+          wv.x = sgd_update(wv.x, gsum.x, lr, wdec, mu, vv.x, plain);
+          wv.y = sgd_update(wv.y, gsum.y, lr, wdec, mu, vv.y, plain);
+          wv.z = sgd_update(wv.z, gsum.z, lr, wdec, mu, vv.z, plain);
+          wv.w = sgd_update(wv.w, gsum.w, lr, wdec, mu, vv.w, plain);
           *reinterpret_cast<float4*>(m) = wv;
+          if (a.vel) *reinterpret_cast<float4*>(a.vel + off) = vv;
         }
         bf16* wf = reinterpret_cast<bf16*>(a.wf[l]);
         wf[(co + 0) * kp + k] = (bf16)wv.x; wf[(co + 1) * kp + k] = (bf16)wv.y;
@@ -1194,8 +1213,14 @@ __global__ __launch_bounds__(RT) void k_rn_sgd(DmlcRnSgdArgs a) {
         const int e = 4 * o4 + j;
         if (e < 650) {
           const size_t off = e < 640 ? (size_t)a.fcw_off + e : (size_t)a.fcb_off + e - 640;
-          if (mode == 1) a.grad[off] = gv[j];
-          else a.master[off] -= lr * (mode == 2 ? a.grad[off] * a.grad_scale : gv[j]);
+          if (mode == 1) {
+            a.grad[off] = gv[j];
+          } else {                               // the weight matrix (e < 640) decays, the bias does not
+            const float g = mode == 2 ? a.grad[off] * a.grad_scale : gv[j];
+            float v = a.vel ? a.vel[off] : 0.f;
+            a.master[off] = sgd_update(a.master[off], g, lr, e < 640 ? wdec : 0.f, mu, v, plain);
+            if (a.vel) a.vel[off] = v;
+          }
         }
       }
     }
@@ -1217,8 +1242,9 @@ __global__ __launch_bounds__(RT) void k_rn_sgd(DmlcRnSgdArgs a) {
     float* mv = a.state + a.mv_off[L] + cc;
     // (a.grad exists only in the data-parallel modes 1/2; the running statistics are only updated
     // by the applying modes)
-    float mg = 0.f, mb = 0.f, gg = 0.f, gb = 0.f, mmv = 0.f, mvv = 0.f;
+    float mg = 0.f, mb = 0.f, gg = 0.f, gb = 0.f, mmv = 0.f, mvv = 0.f, vg = 0.f, vb = 0.f;
     if (mode != 1) { mg = a.master[og]; mb = a.master[ob]; mmv = *mm; mvv = *mv; }
+    if (mode != 1 && a.vel) { vg = a.vel[og]; vb = a.vel[ob]; }
     if (mode == 2) { gg = a.grad[og]; gb = a.grad[ob]; }
     float lsv = 0.f, csv = 0.f;
     if (L == 0 && apply)
@@ -1228,8 +1254,9 @@ __global__ __launch_bounds__(RT) void k_rn_sgd(DmlcRnSgdArgs a) {
         a.grad[og] = (float)r2;
         a.grad[ob] = (float)r1;
       } else {
-        a.master[og] = mg - lr * (mode == 2 ? gg * a.grad_scale : (float)r2);
-        a.master[ob] = mb - lr * (mode == 2 ? gb * a.grad_scale : (float)r1);
+        a.master[og] = sgd_update(mg, mode == 2 ? gg * a.grad_scale : (float)r2, lr, 0.f, mu, vg, plain);   // rank 1:
+        a.master[ob] = sgd_update(mb, mode == 2 ? gb * a.grad_scale : (float)r1, lr, 0.f, mu, vb, plain);   // no decay
+        if (a.vel) { a.vel[og] = vg; a.vel[ob] = vb; }
         const double inv = (double)a.inv_n[L];
         const double mean = s1 * inv;
         double var = s2 * inv - mean * mean;
@@ -1396,6 +1423,7 @@ static int split_for(int n) {                 // slabs per thread <= 8
 hipError_t dmlc_rn_sgd(DmlcRnSgdArgs* a, hipStream_t s) {
   if (a->layer_lo < 0 || a->layer_hi > DMLC_RN_LAYERS || a->layer_lo > a->layer_hi) return hipErrorInvalidValue;
   if (!a->tail && (a->mode == 1 || a->mode == 2 || a->mode == 3)) return hipErrorInvalidValue;   // partial: mode 0
+  if (a->momentum != 0.f && !a->vel && (a->mode == 0 || a->mode == 2)) return hipErrorInvalidValue;   // no velocity
   int blocks = 0;
   for (int l = 0; l < DMLC_RN_LAYERS; ++l) {      // layers outside the range get no blocks
     a->split[l] = split_for(a->G[l]);

@@ -201,6 +201,32 @@ def load_model_tensors(tensors: Dict[str, torch.Tensor], flat_size: Optional[int
     return flat, step, gen
 
 
+MOMENTUM_SLOT = "/Momentum"     # TF slot naming: MomentumOptimizer keeps "<variable name>/Momentum"
+
+
+def momentum_tensors(velocity: torch.Tensor, specs) -> Dict[str, torch.Tensor]:
+    """The velocity of a flat parameter buffer as one fp32 slot per trainable variable."""
+    vel = velocity.detach().float().cpu()
+    return {s.name + MOMENTUM_SLOT: vel[s.offset:s.offset + s.numel].view(s.shape).clone() for s in specs}
+
+
+def load_momentum_tensors(tensors: Dict[str, torch.Tensor], specs, flat_size: int) -> Optional[torch.Tensor]:
+    """Inverse of :func:`momentum_tensors`: the flat velocity, or None when the checkpoint holds no
+    slots (a plain-SGD checkpoint).  Some slots without the others is an error."""
+    if not any(s.name + MOMENTUM_SLOT in tensors for s in specs):
+        return None
+    vel = torch.zeros(flat_size, dtype=torch.float32)
+    for s in specs:
+        name = s.name + MOMENTUM_SLOT
+        if name not in tensors:
+            raise KeyError(f"checkpoint is missing {name}")
+        t = tensors[name]
+        if tuple(t.shape) != tuple(s.shape):
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != model shape {s.shape}")
+        vel[s.offset:s.offset + s.numel] = t.float().reshape(-1)
+    return vel
+
+
 def module_tensors(model, global_step: int, generation_num: int = 0) -> Dict[str, torch.Tensor]:
     """Checkpoint dict of an eager model with flat buffers (``flat`` + optional ``state``)."""
     d = {s.name: model.flat.detach().cpu()[s.offset:s.offset + s.numel].view(s.shape).clone() for s in model.specs}

@@ -63,6 +63,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="linear: learning_rate * global_batch / lr_base_batch (large-batch recipe)")
     p.add_argument("--lr_base_batch", type=int, default=d.lr_base_batch)
     p.add_argument("--warmup_steps", type=int, default=d.warmup_steps, help="linear LR warm-up steps")
+    p.add_argument("--momentum", type=float, default=d.momentum,
+                   help="SGD momentum in [0, 1): v = momentum * v + g, w -= lr * v (0: plain SGD)")
+    p.add_argument("--weight_decay", type=float, default=d.weight_decay,
+                   help="L2 weight decay added to the gradient of conv kernels and fc weight matrices "
+                        "(biases and BatchNorm gamma / beta are not decayed)")
     p.add_argument("--output_every", type=int, default=d.output_every)
     p.add_argument("--eval_every", type=int, default=d.eval_every)
     p.add_argument("--eval_batches", type=int, default=d.eval_batches)

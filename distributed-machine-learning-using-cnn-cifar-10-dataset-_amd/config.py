@@ -60,6 +60,10 @@ class TrainConfig:
     lr_scaling: str = "none"              # 'none' (reference) | 'linear'
     lr_base_batch: int = BATCH_SIZE       # the batch learning_rate was tuned for (the reference's 128)
     warmup_steps: int = 0
+    # SGD momentum and L2 weight decay (0, 0: the reference's plain gradient descent):
+    # v <- momentum * v + (g + weight_decay * w), w <- w - lr * v; the decay skips rank-1 parameters
+    momentum: float = 0.0
+    weight_decay: float = 0.0
     output_every: int = OUTPUT_EVERY
     eval_every: int = EVAL_EVERY
     eval_batches: int = 0                 # 0 = full test set; 1 = reference fidelity (one batch)

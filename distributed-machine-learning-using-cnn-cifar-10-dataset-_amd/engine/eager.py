@@ -5,7 +5,8 @@ Used for (a) the CPU "plumbing" configuration (BASELINE config 1), (b) the fp32-
 step by step from here, optionally captured into one HIP graph), (c) the framework-default
 comparison line of the benchmark, and (d) the numerics oracle for the fused engines.  Semantics follow the reference training step
 (/root/reference/cifar10cnn.py:159-164, :230): sparse softmax cross-entropy (mean), plain SGD,
-staircase LR decay, global_step++.  Data parallelism is synchronous: the flat gradient is
+staircase LR decay, global_step++; ``momentum`` / ``weight_decay`` (both 0 by default) turn the
+update into SGD with momentum and L2 decay of the rank >= 2 parameters.  Data parallelism is synchronous: the flat gradient is
 all-reduced in two buckets (fc first, then conv — SURVEY.md §2.D) and averaged.
 """
 from __future__ import annotations
@@ -19,6 +20,7 @@ import torch.distributed as dist
 from .. import config as C
 from ..data.order import OrderSpec, apply_augment, unpack_aug
 from ..models import build_model
+from ..models.cifar_cnn import decay_mask
 
 
 class EagerTrainer:
@@ -27,8 +29,17 @@ class EagerTrainer:
                  lr: float = C.LEARNING_RATE, lr_decay: float = C.LR_DECAY,
                  decay_steps: float = C.NUM_GENS_TO_WAIT, staircase: bool = True, relu_logits: bool = True,
                  crop: int = C.CROP_HEIGHT, seed: int = 0, flat_params: Optional[torch.Tensor] = None,
-                 augment: bool = False, graph: bool = False, warmup_steps: int = 0, backend: str = "torch"):
+                 augment: bool = False, graph: bool = False, warmup_steps: int = 0, backend: str = "torch",
+                 momentum: float = 0.0, weight_decay: float = 0.0):
         self.device = torch.device(device)
+        if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
+            raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
+        # SGD with momentum / L2 weight decay (both 0: the reference's plain update, unchanged):
+        #   v <- momentum * v + (g + wd_eff * w);  w <- w - lr * v
+        # wd_eff = weight_decay on the rank >= 2 specs only (models/cifar_cnn.py decay_mask)
+        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self._vel = {}          # parameter -> velocity, created at its first update
+        self._wd_mask = {}      # parameter -> weight_decay * decay mask
         if backend == "hip_f32" and (self.device.type != "cuda" or dtype != "fp32"):
             raise ValueError("the hip_f32 backend is the fp32 GPU path (device cuda, dtype fp32)")
         self.backend = backend
@@ -111,6 +122,32 @@ class EagerTrainer:
             if b is None:
                 break
 
+    def _decay_term(self, p) -> torch.Tensor:
+        """weight_decay * decay mask of parameter ``p`` (the flat buffer: by its specs; any other
+        parameter: by its own rank)."""
+        if p not in self._wd_mask:
+            if p is getattr(self.model, "flat", None):
+                mask = decay_mask(self.model.specs, p.numel()).to(p.device)
+            else:
+                mask = torch.full_like(p, 1.0 if p.dim() >= 2 else 0.0)
+            self._wd_mask[p] = self.weight_decay * mask
+        return self._wd_mask[p]
+
+    def velocity(self, p) -> torch.Tensor:
+        if p not in self._vel:
+            self._vel[p] = torch.zeros_like(p)
+        return self._vel[p]
+
+    def _momentum_update(self, p, lr):
+        """v <- momentum * v + (g + wd_eff * w); w <- w - lr * v (``lr``: float or 0-d device tensor)."""
+        d = torch.addcmul(p.grad, self._decay_term(p), p) if self.weight_decay else p.grad
+        if self.momentum:
+            d = self.velocity(p).mul_(self.momentum).add_(d)
+        if torch.is_tensor(lr):
+            p.addcmul_(d, lr, value=-1.0)
+        else:
+            p.add_(d, alpha=-lr)
+
     def _fwd_bwd_sgd(self, x, y, lr):
         """One training step's device work; ``lr`` is a float or a 0-d device tensor."""
         use_amp = self.dtype == "bf16" and self.device.type == "cuda"
@@ -122,7 +159,9 @@ class EagerTrainer:
         with torch.no_grad():
             for p in self.model.parameters():
                 if p.grad is not None:
-                    if torch.is_tensor(lr):
+                    if self.momentum or self.weight_decay:
+                        self._momentum_update(p, lr)
+                    elif torch.is_tensor(lr):
                         p.addcmul_(p.grad, lr, value=-1.0)
                     else:
                         p.add_(p.grad, alpha=-lr)
@@ -174,8 +213,19 @@ class EagerTrainer:
     def flat_params(self) -> torch.Tensor:
         return self.model.flat.detach().cpu().clone()
 
+    def velocity_params(self) -> Optional[torch.Tensor]:
+        """The velocity of the flat parameter buffer (CPU copy); None without momentum."""
+        return self.velocity(self.model.flat).detach().cpu().clone() if self.momentum else None
+
     @torch.no_grad()
-    def load_flat_params(self, flat: torch.Tensor, step: Optional[int] = None):
+    def load_velocity(self, vel: torch.Tensor):
+        self.velocity(self.model.flat).copy_(vel.to(self.model.flat.device, self.model.flat.dtype))
+
+    @torch.no_grad()
+    def load_flat_params(self, flat: torch.Tensor, step: Optional[int] = None,
+                         velocity: Optional[torch.Tensor] = None):
+        if velocity is not None:
+            self.load_velocity(velocity)
         self.model.flat.copy_(flat.to(self.model.flat.device, self.model.flat.dtype))
         if hasattr(self.model, "after_load"):
             self.model.after_load()

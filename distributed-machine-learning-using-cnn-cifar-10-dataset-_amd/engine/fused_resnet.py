@@ -14,7 +14,8 @@ all HIP kernels of csrc/kernels/resnet.hip, captured as one HIP graph:
        l=18..0   wgrad_l, split-K fp32 slabs: in the same launch as dgrad_l (block roles), or on a
                  side stream (a second graph branch, wgrad_branch=True)
   sgd            slab reduction + SGD (conv, BN gamma/beta, fc) + BN running statistics (momentum 0.1)
-                 + bf16 weight shadows + global_step++ + stats ring
+                 + bf16 weight shadows + global_step++ + stats ring; with ``momentum`` /
+                 ``weight_decay`` the same kernel keeps the velocity and adds the L2 term
 
 Batch statistics are per rank (as in the eager model under DP).  With data parallelism the SGD runs
 in two halves around ONE all-reduce of the 1.1 MB flat gradient (mode 1 -> RCCL -> mode 2).
@@ -110,7 +111,10 @@ class FusedResNetEngine:
                  stats_len: int = 4096, comm_dtype: str = "fp32", wgrad_branch: Optional[bool] = None,
                  allreduce: str = "auto", capture_comm: Optional[bool] = None, dp_force: bool = False,
                  warmup_steps: int = 0,
-                 merged_bwd: Optional[bool] = None, bwd_img_level: int = 1, sgd_split: bool = False):
+                 merged_bwd: Optional[bool] = None, bwd_img_level: int = 1, sgd_split: bool = False,
+                 momentum: float = 0.0, weight_decay: float = 0.0, velocity: Optional[torch.Tensor] = None):
+        if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
+            raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
         ops = _ops()
         self.ops = ops
         self.device = torch.device(device or "cuda")
@@ -148,6 +152,14 @@ class FusedResNetEngine:
             s0 = state
         self.master = f0.to(dev, torch.float32).contiguous().clone()
         self.state = s0.to(dev, torch.float32).contiguous().clone()
+        # SGD momentum / L2 weight decay, applied by the SGD kernel (v <- momentum * v + (g + wd_eff * w),
+        # w <- w - lr * v; wd_eff = weight_decay on the conv kernels and the fc weights only).  The
+        # velocity lives in the layout of master; a static buffer, so graphs and chains capture it, and
+        # under data parallelism every replica applies the same reduced gradient to the same velocity
+        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self.vel = torch.zeros_like(self.master) if self.momentum else None
+        if velocity is not None and self.vel is not None:
+            self.vel.copy_(velocity.to(dev, torch.float32))
         # gradient all-reduce (N>1): xGMI peer-to-peer kernel over an IPC-shared buffer when it
         # self-tests and measures faster than RCCL (parallel/xgmi.py), else RCCL
         self.xgmi, self.comm_info = None, {"allreduce": "rccl" if self.dp else "none"}
@@ -357,7 +369,7 @@ class FusedResNetEngine:
                         self.red, self.fc_part, self.loss_img, self.correct_img, self.step_t, self.ticket, self.stats,
                         mode, self.lr0, self.decay, self.decay_steps, self.staircase, R.BN_MOMENTUM, self.warmup,
                         layers[0], layers[1], tail, self.Bv,
-                        None)
+                        None, self.vel, self.momentum, self.weight_decay)
 
     def _allreduce(self, t: torch.Tensor):
         import torch.distributed as dist
@@ -524,10 +536,17 @@ class FusedResNetEngine:
     def flat_params(self) -> torch.Tensor:
         return self.master.detach().cpu()
 
-    def load_flat_params(self, flat: torch.Tensor, step: Optional[int] = None, state: Optional[torch.Tensor] = None):
+    def velocity_params(self) -> Optional[torch.Tensor]:
+        """The momentum velocity in the layout of :meth:`flat_params` (CPU copy); None without momentum."""
+        return None if self.vel is None else self.vel.detach().cpu()
+
+    def load_flat_params(self, flat: torch.Tensor, step: Optional[int] = None, state: Optional[torch.Tensor] = None,
+                         velocity: Optional[torch.Tensor] = None):
         self.master.copy_(flat.to(self.device, torch.float32))
         if state is not None:
             self.state.copy_(state.to(self.device, torch.float32))
+        if velocity is not None and self.vel is not None:
+            self.vel.copy_(velocity.to(self.device, torch.float32))
         if step is not None:
             self.set_step(step)
         self.refresh_shadows()

@@ -48,6 +48,9 @@ class _FusedAdapter:
     TUNE_ITERS = 20
 
     def __init__(self, cfg: C.TrainConfig, info: D.DistInfo, data, labels):
+        if cfg.momentum or cfg.weight_decay:
+            raise ValueError("--momentum / --weight_decay: the fused CIFAR-CNN step applies plain SGD only; "
+                             "use --impl=eager (or --dtype=fp32) with --model=cifar_cnn, or --model=resnet20")
         from .fused import FusedCifarEngine
         self.eng = FusedCifarEngine(cfg.batch_size, data, labels, device=info.device, world_size=info.world_size,
                                     rank=max(0, info.rank), seed=cfg.seed, lr=C.effective_lr(cfg, info.world_size), warmup_steps=cfg.warmup_steps,
@@ -157,7 +160,7 @@ class _FusedResNetAdapter(_FusedAdapter):
                                      rank=max(0, info.rank), seed=cfg.seed, lr=C.effective_lr(cfg, info.world_size), warmup_steps=cfg.warmup_steps,
                                      lr_decay=cfg.lr_decay, decay_steps=cfg.num_gens_to_wait,
                                      staircase=cfg.lr_schedule == "staircase", comm_dtype=cfg.comm_dtype,
-                                     allreduce=cfg.allreduce)
+                                     allreduce=cfg.allreduce, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
         self.cfg = cfg
         self.graph = cfg.graph
         self.specs, self.state_specs = R.PARAM_SPECS, R.STATE_SPECS
@@ -166,6 +169,8 @@ class _FusedResNetAdapter(_FusedAdapter):
         d = CK.model_tensors(self.eng.flat_params(), self.eng.host_step, 0, specs=self.specs)
         st = self.eng.state.detach().cpu()
         d.update({s.name: st[s.offset:s.offset + s.numel].view(s.shape).clone() for s in self.state_specs})
+        if self.eng.vel is not None:                 # momentum: one "<variable>/Momentum" slot each
+            d.update(CK.momentum_tensors(self.eng.velocity_params(), self.specs))
         return d
 
     def load_tf_tensors(self, tensors):
@@ -175,11 +180,24 @@ class _FusedResNetAdapter(_FusedAdapter):
             if s.name not in tensors:
                 raise KeyError(f"checkpoint is missing {s.name}")
             state[s.offset:s.offset + s.numel] = tensors[s.name].float().reshape(-1)
-        self.eng.load_flat_params(flat, step, state=state)
+        vel = _restored_velocity(tensors, self.specs, flat.numel()) if self.eng.vel is not None else None
+        self.eng.load_flat_params(flat, step, state=state, velocity=vel)
 
     def broadcast_from_chief(self, info):
         D.broadcast_(self.eng.state, info)
+        if self.eng.vel is not None:                 # the chief's restored velocity, not this rank's zeros
+            D.broadcast_(self.eng.vel, info)
         super().broadcast_from_chief(info)
+
+
+def _restored_velocity(tensors, specs, flat_size: int) -> torch.Tensor:
+    """The velocity of a run with momentum from a checkpoint: its ``*/Momentum`` slots, or zeros (and
+    one log line) when it has none -- continuing a plain-SGD checkpoint with momentum is legitimate."""
+    vel = CK.load_momentum_tensors(tensors, specs, flat_size)
+    if vel is None:
+        print("[dmlc] the checkpoint holds no */Momentum slots: the velocity starts from zero", flush=True)
+        vel = torch.zeros(flat_size, dtype=torch.float32)
+    return vel
 
 
 class _EagerAdapter:
@@ -192,7 +210,8 @@ class _EagerAdapter:
                                lr=C.effective_lr(cfg, info.world_size), warmup_steps=cfg.warmup_steps, lr_decay=cfg.lr_decay, decay_steps=cfg.num_gens_to_wait,
                                staircase=cfg.lr_schedule == "staircase", relu_logits=cfg.relu_logits,
                                crop=cfg.crop, seed=cfg.seed, augment=cfg.augment, backend=backend,
-                               graph=backend == "hip_f32" and cfg.graph and info.world_size == 1)
+                               graph=backend == "hip_f32" and cfg.graph and info.world_size == 1,
+                               momentum=cfg.momentum, weight_decay=cfg.weight_decay)
         self.specs = self.tr.model.specs
 
     def start(self, log=print):
@@ -224,15 +243,22 @@ class _EagerAdapter:
                 "accuracy": float(self.tr.last_acc), "lr": self.tr.lr(self.tr.global_step - 1)}
 
     def tf_tensors(self) -> Dict[str, torch.Tensor]:
-        return CK.module_tensors(self.tr.model, self.tr.global_step, 0)
+        d = CK.module_tensors(self.tr.model, self.tr.global_step, 0)
+        if self.tr.momentum:                         # one "<variable>/Momentum" slot each
+            d.update(CK.momentum_tensors(self.tr.velocity_params(), self.specs))
+        return d
 
     def load_tf_tensors(self, tensors):
         self.tr.global_step = CK.load_module_tensors(self.tr.model, tensors)
+        if self.tr.momentum:
+            self.tr.load_velocity(_restored_velocity(tensors, self.specs, self.tr.model.flat.numel()))
 
     def broadcast_from_chief(self, info):
         dev = info.device if info.backend == "nccl" else torch.device("cpu")
         m = self.tr.model
         bufs = [m.flat.data] + ([m.state] if hasattr(m, "state") else [])
+        if self.tr.momentum:                         # the chief's restored velocity, not this rank's zeros
+            bufs.append(self.tr.velocity(m.flat))
         step = torch.tensor([self.tr.global_step], dtype=torch.int64)
         for b in bufs + [step]:
             t = b.to(dev)
@@ -260,7 +286,8 @@ def pick_impl(cfg: C.TrainConfig, device: torch.device) -> str:
         return cfg.impl
     if device.type == "cuda" and cfg.model == "cifar_cnn" and cfg.dtype in ("bf16", "fp8") and cfg.crop == 24:
         # any batch size: masked tail rows; --augment: per-image crop + flip in the kernels (engine/fused.py)
-        return "fused"
+        # --momentum / --weight_decay: the fused CNN step only has plain SGD -> torch ops
+        return "eager" if cfg.momentum or cfg.weight_decay else "fused"
     if device.type == "cuda" and cfg.model == "cifar_cnn" and cfg.dtype == "fp32":
         return "hipf32"                   # reference precision on the fp32 HIP kernels (ops/f32.py)
     if (device.type == "cuda" and cfg.model == "resnet20" and cfg.dtype == "bf16" and cfg.crop == 32
@@ -398,8 +425,10 @@ class Session:
         start = eng.global_step
         _fault_injection(eng.global_step, self.info.rank, eng)
         eng.start(log=self.log)
+        opt = (f" momentum={cfg.momentum:g}" if cfg.momentum else "") + \
+              (f" weight_decay={cfg.weight_decay:g}" if cfg.weight_decay else "")
         self.log(f"[dmlc] engine={self.impl} model={cfg.model} dtype={cfg.dtype} batch={cfg.batch_size} "
-                 f"world={self.info.world_size} device={self.info.device}")
+                 f"world={self.info.world_size} device={self.info.device}{opt}")
         self.log("Starting Training")
         last_t, last_step = time.time(), eng.global_step
         result = {}

@@ -45,6 +45,20 @@ class ParamSpec:
         return int(math.prod(self.shape))
 
 
+def decay_mask(specs, size: int | None = None) -> torch.Tensor:
+    """Which elements of the flat parameter buffer L2 weight decay applies to: fp32 [size], 1 over
+    every spec of rank >= 2 (conv kernels, fc weight matrices), 0 over the rank-1 specs (biases, BN
+    gamma / beta) and the alignment padding.  ``size`` defaults to the end of the last spec rounded
+    up to ALIGN (the models' FLAT_SIZE)."""
+    if size is None:
+        size = max(-(-(s.offset + s.numel) // ALIGN) * ALIGN for s in specs)
+    mask = torch.zeros(size, dtype=torch.float32)
+    for s in specs:
+        if len(s.shape) >= 2:
+            mask[s.offset:s.offset + s.numel] = 1.0
+    return mask
+
+
 def _build_specs(crop: int = C.CROP_HEIGHT) -> Tuple[List[ParamSpec], int]:
     flat = (crop // 4) * (crop // 4) * 64  # two stride-2 pools: 24 → 12 → 6 ; 6*6*64 = 2304
     raw = [

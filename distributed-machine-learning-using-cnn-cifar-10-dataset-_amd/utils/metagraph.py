@@ -316,6 +316,8 @@ def _cnn_forward(G: _Graph, v: Dict[str, Dict[str, str]], x: str, batch: int, re
 
 
 def _var_init(name: str) -> Tuple[str, float]:
+    if name.endswith("/Momentum"):                  # optimizer slot: zero velocity
+        return ("const", 0.0)
     if name.endswith("_kernel") or "full_weight" in name or name.endswith("/weights"):
         return ("trunc_normal", 0.05)
     if name in ("global_step", "Variable"):
