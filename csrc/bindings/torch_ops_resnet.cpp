@@ -1,4 +1,4 @@
-// torch.ops.dmlc.rn_* bindings of the fused ResNet-20 kernels (csrc/kernels/resnet.hip).
+// torch.ops.dmlc.rn_* bindings of the fused ResNet-20 kernels (csrc/kernels/resnet.hip, resnet_head.hip, resnet_sgd.hip).
 //
 // Same contract as torch_ops.cpp: every launch is preceded by a full check of device, dtype,
 // contiguity and the exact shapes implied by the layer geometry (one of the six ResNet-20 conv
@@ -30,7 +30,7 @@ Geom geom(int64_t cin, int64_t cout, int64_t hin, int64_t stride) {
 }
 
 // per-layer statistics accumulators: fixed-point int64 [NSLOT][256] (integer parts of sum / sum of
-// squares or R1 / R2 at [0, 128), their 48-bit fractions at [128, 256); resnet.hip fx_add)
+// squares or R1 / R2 at [0, 128), their 48-bit fractions at [128, 256); rn_stats.h fx_add)
 void check_stat(const Tensor& t, const char* n) { check_numel(t, n, at::kLong, DMLC_RN_NSLOT * 256); }
 #define STAT_PTR(t) reinterpret_cast<long long*>((t).data_ptr<int64_t>())
 

@@ -1,4 +1,4 @@
-// Host-side launch API of the fused ResNet-20 kernels (csrc/kernels/resnet.hip).
+// Host-side launch API of the fused ResNet-20 kernels (csrc/kernels/resnet.hip, resnet_head.hip, resnet_sgd.hip).
 //
 // Conventions: activations NHWC bf16; per-layer BatchNorm statistics live in NSLOT fixed-point slots
 // per layer (slot = producing block & 7; int64 [NSLOT][hi 128 | lo 128], integer part + 48-bit

@@ -1,4 +1,4 @@
-"""Integer oracle of the fused ResNet-20 kernels (csrc/kernels/resnet.hip), ONE kernel at a time: the
+"""Integer oracle of the fused ResNet-20 kernels (csrc/kernels/resnet*.hip), ONE kernel at a time: the
 3x3 convolution at stride 1 / 2 with its input and weight gradients, the BatchNorm prologue / epilogue
 coefficients, the option-A shortcut and its gradient, the per-image split-K slabs, both bf16 weight
 shadows and the head.  Plain torch on the CPU in fp64, written from the definitions in
@@ -26,7 +26,7 @@ import types
 import torch
 
 F64 = torch.float64
-BN_EPS = 1e-3                  # models/resnet.py BN_EPS, resnet.hip BN_EPS
+BN_EPS = 1e-3                  # models/resnet.py BN_EPS, rn_stats.h BN_EPS
 NSLOT = 8                      # statistics slots per layer
 FX_ONE = float(2 ** 48)        # fraction unit of the fixed-point statistics
 LIM = 2 ** 24                  # fp32 sums of integers are exact below this
@@ -114,7 +114,7 @@ def conv3x3_wgrad(x, g, stride):
 
 
 # --------------------------------------------------------------------------------------------------
-# BatchNorm coefficients from the statistics TOTALS (resnet.hip bn_mean_rstd / bnb_coeffs)
+# BatchNorm coefficients from the statistics TOTALS (rn_stats.h bn_mean_rstd / bnb_coeffs)
 def bn_coeffs(stat, red, gamma, N, f32=False):
     """``stat`` = (sum z, sum z^2), ``red`` = (R1 = sum g_y, R2 = sum g_y xhat) or None, per channel,
     over N elements.  Returns (mean, rstd, A, Bc, Cc): y = gamma rstd (z - mean) + beta forward,
@@ -259,7 +259,7 @@ def head_exact(z, mean, rstd, gamma, beta, sc, fcw, fcb, labels, inv_batch, nval
 
 
 # --------------------------------------------------------------------------------------------------
-# fixed-point statistics slots (host mirror of resnet.hip fx_add / fx_total, written here from the
+# fixed-point statistics slots (host mirror of rn_stats.h fx_add / fx_total, written here from the
 # header's description: int64 integer part at [e], 48-bit fraction at [128 + e], 8 slots per layer)
 def fx_split(x):
     x = x.to(F64)
@@ -290,12 +290,12 @@ def encode_slots(t1, t2, gen):
 
 
 def fx_total(slots):
-    """Decoded totals fp64 [128] of slots [NSLOT, 256], as resnet.hip fx_total forms them."""
+    """Decoded totals fp64 [128] of slots [NSLOT, 256], as rn_stats.h fx_total forms them."""
     return slots[:, :128].sum(0).double() + slots[:, 128:].sum(0).double() * (1.0 / FX_ONE)
 
 
 def emulate_mean_rstd(slots, C, inv_n):
-    """resnet.hip bn_mean_rstd on the CPU: fp64 arithmetic without contraction, float results."""
+    """rn_stats.h bn_mean_rstd on the CPU: fp64 arithmetic without contraction, float results."""
     tot = fx_total(slots)
     inv = float(torch.tensor(inv_n, dtype=torch.float32))
     m = tot[:C] * inv

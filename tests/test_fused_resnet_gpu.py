@@ -1,4 +1,4 @@
-"""Fused ResNet-20 HIP kernels (csrc/kernels/resnet.hip) vs the fp32 PyTorch model (models/resnet.py,
+"""Fused ResNet-20 HIP kernels (csrc/kernels/resnet*.hip) vs the fp32 PyTorch model (models/resnet.py,
 train-mode BatchNorm): forward logits, every parameter gradient, one SGD step incl. BN running
 statistics, graph replay vs eager launches, and a short convergence run."""
 import pytest
@@ -169,7 +169,7 @@ def test_graph_replay_matches_eager_launches_bitwise(B):
 
 
 def test_fixed_point_bn_sums_match_activations():
-    """The fixed-point slot totals (integer atomics, resnet.hip fx_add) equal an fp64 sum of the stored
+    """The fixed-point slot totals (integer atomics, rn_stats.h fx_add) equal an fp64 sum of the stored
     pre-BN activations per channel, up to their bf16 rounding."""
     B = 64
     data, labels = _data(4 * B, seed=9)

@@ -128,7 +128,7 @@ def test_fused_resnet_layer_table_matches_model():
 
 
 def test_fixed_point_bn_slots_are_order_independent():
-    """The fused engine's BatchNorm sums are fixed-point (resnet.hip fx_add / fx_total): integer part +
+    """The fused engine's BatchNorm sums are fixed-point (rn_stats.h fx_add / fx_total): integer part +
     48-bit fraction per fp32 partial.  Any add order gives the same bits, the total matches an fp64 sum,
     and a poisoned slot (non-finite partial) decodes to NaN.  Host mirror of the encoding."""
     from dmlc.engine import fused_resnet as FR

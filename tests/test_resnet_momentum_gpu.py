@@ -1,4 +1,4 @@
-"""SGD momentum + L2 weight decay inside the fused ResNet-20 SGD kernel (k_rn_sgd, csrc/kernels/resnet.hip):
+"""SGD momentum + L2 weight decay inside the fused ResNet-20 SGD kernel (k_rn_sgd, csrc/kernels/resnet_sgd.hip):
 
     v <- mu * v + (g + wd_eff * w);  w <- w - lr * v;  wd_eff = wd on conv kernels / fc weights, else 0
 

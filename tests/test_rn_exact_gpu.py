@@ -1,4 +1,4 @@
-"""Exact per-kernel tests of the fused ResNet-20 kernels (csrc/kernels/resnet.hip): rn_fwd, rn_dgrad,
+"""Exact per-kernel tests of the fused ResNet-20 kernels (csrc/kernels/resnet*.hip): rn_fwd, rn_dgrad,
 rn_wgrad, rn_bwd (merged and per-image), rn_head, and the slab reduction / weight shadows of rn_sgd.
 
 Every rn_* op takes its statistics slots, gamma and beta as input tensors, so each test launches ONE
