@@ -59,28 +59,16 @@ from __future__ import annotations
 import dataclasses
 import math
 import os
-from typing import Dict, List, Optional
+from typing import Optional
 
 import torch
 
 from .. import config as C
 from ..parallel.dist import quiesce_for_capture
-from ..data.order import OrderSpec
 from ..models import cifar_cnn as M
-from ..ops import _ext
+from .base import FusedEngineBase
 from .plan import (ERR_WORD, FC_SYNC_WORDS, HAND_WORDS, TICKET_WORDS, VARIANT_DEFAULTS, WBAR_WORDS,  # noqa: F401
                    head_rows, plan_step)
-
-OPS = None
-
-
-def _ops():
-    global OPS
-    if OPS is None:
-        _ext.hip()
-        OPS = torch.ops.dmlc
-    return OPS
-
 
 SEG_OFF = [s.offset for s in M.PARAM_SPECS]
 # the engine attributes the dict-taking ops read by name (FusedCifarEngine.buf)
@@ -101,7 +89,7 @@ def _gemm_params(M_, N_, K_, lda, a_kmajor, ldb, b_kmajor, ldc, c_mode, ksplit=1
 FC1_NUMEL = 2304 * 384
 
 
-class FusedCifarEngine:
+class FusedCifarEngine(FusedEngineBase):
     """Owns every device buffer of the fused step.  Not an nn.Module: parameters live in one flat
     fp32 buffer (``self.master``) in the TF checkpoint layout; see models/cifar_cnn.py."""
 
@@ -115,12 +103,11 @@ class FusedCifarEngine:
                  dp_schedule: str = "serial", dp_force: bool = False, warmup_steps: int = 0,
                  conv_split: Optional[int] = None, conv1_split: Optional[int] = None,
                  dgrad_split: Optional[int] = None, variant: Optional[dict] = None, augment: bool = False):
-        self.ops = _ops()
-        self.device = torch.device(device or "cuda")
+        super().__init__(device=device, world_size=world_size, rank=rank, process_group=process_group, seed=seed,
+                         comm_dtype=comm_dtype, lr=lr, lr_decay=lr_decay, decay_steps=decay_steps,
+                         staircase=staircase, warmup_steps=warmup_steps, dp_force=dp_force,
+                         capture_comm=capture_comm, stats_len=stats_len)
         dev = self.device
-        self.world_size, self.rank, self.pg = world_size, rank, process_group
-        self.lr0, self.decay, self.decay_steps, self.staircase = lr, lr_decay, decay_steps, staircase
-        self.warmup = float(warmup_steps)      # linear LR warm-up (large-batch recipe), in the SGD kernel
         self.relu_logits = relu_logits
         self.cy, self.cx = crop_offset
         # per-image random crop + flip of the training batches (api.h DmlcConv1FwdArgs::aug); the
@@ -128,8 +115,6 @@ class FusedCifarEngine:
         self.augment = bool(augment)
         if self.augment and tuple(crop_offset) != (4, 4):
             raise ValueError("augment needs the 24x24 crop: crop_offset must be (4, 4)")
-        self.comm_dtype = comm_dtype
-        self.seed = seed
         self.dtype = dtype
 
         # --- the planner's inputs: everything read from the process, the device and the fabric -------
@@ -137,25 +122,15 @@ class FusedCifarEngine:
         cus = torch.cuda.get_device_properties(dev).multi_processor_count if on_gpu else 0
         ndev = torch.cuda.device_count() if on_gpu else 0
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world_size))
-        dp = world_size > 1 or dp_force          # (StepPlan.dp)
-        if capture_comm is None:     # RCCL collectives go into the step graph unless told otherwise
-            capture_comm = dp and self._pg_backend() == "nccl"
-        self.capture_comm = bool(capture_comm)
         if flat_params is None:
             flat_params = M.init_flat_params(torch.Generator().manual_seed(seed))
         n_flat = flat_params.numel()
-        # gradient all-reduce: xGMI peer-to-peer kernel over an IPC-shared grad buffer when every
-        # rank can map every peer and it measures faster than RCCL (parallel/xgmi.py), else RCCL
-        self.xgmi, self.comm_info = None, {"allreduce": "rccl" if dp else "none"}
         self._buckets = {True: (M.FC_BUCKET_OFFSET, n_flat - M.FC_BUCKET_OFFSET), False: (0, M.FC_BUCKET_OFFSET)}
-        if world_size > 1 and on_gpu and comm_dtype in ("fp32", "bf16") and allreduce != "rccl":
-            from ..parallel import xgmi as X
-            # timed on the call pattern the step will issue: one whole-buffer all-reduce (serial) or
-            # the fc bucket then the conv bucket (overlap)
-            pattern = ([(0, n_flat)] if dp_schedule == "serial" else [self._buckets[True], self._buckets[False]])
-            self.xgmi, self.comm_info = X.select(n_flat, rank, world_size, dev, pattern, mode=allreduce,
-                                                 group=process_group, wire=comm_dtype, captured=self.capture_comm)
-        elif dp_force and world_size == 1 and allreduce == "xgmi" and on_gpu:
+        # the call pattern the step will issue: one whole-buffer all-reduce (serial) or the fc bucket
+        # then the conv bucket (overlap)
+        self._select_xgmi(n_flat, [(0, n_flat)] if dp_schedule == "serial"
+                          else [self._buckets[True], self._buckets[False]], allreduce)
+        if dp_force and world_size == 1 and allreduce == "xgmi" and on_gpu:
             # a one-rank xGMI context (no peers): the DP step's exchange kernel on a single GPU
             from ..parallel import xgmi as X
             self.xgmi = X.XgmiAllReduce(n_flat, 0, 1, None, wire=comm_dtype)
@@ -169,17 +144,11 @@ class FusedCifarEngine:
         self.plan = plan_step(**self.plan_inputs)
         for f in dataclasses.fields(self.plan):
             setattr(self, f.name, getattr(self.plan, f.name))
-        B, Bv = self.B, self.Bv
+        B = self.B
         self.keep_dp1 = False          # tests: also write the pool1 gradient to global memory
 
         # --- data (device resident) ---------------------------------------------------------
-        assert data.dtype == torch.uint8 and tuple(data.shape[1:]) == (32, 32, 3)
-        self.data = data.to(dev).contiguous()
-        self.labels = labels.to(dev, torch.int32).contiguous()
-        self.n_data = self.data.shape[0]
-        self.order = OrderSpec(self.n_data, Bv, world_size, rank, seed)
-        self.period = self.order.period          # steps per epoch
-        self.order_desc = self.order.descriptor()   # host int64 [6]: the generated order
+        self._init_batch(data, labels, B, self.Bv)
         # this step's batch rows (int32 [B], rows >= Bv repeat the last): written for step s+1 by the
         # finalizing SGD launch of step s (cnn_sgd.hip), so each data kernel reads one index per row;
         # set from the host whenever the step counter is set from the host
@@ -192,11 +161,7 @@ class FusedCifarEngine:
 
         # --- parameters + shadows -------------------------------------------------------------
         self.master = flat_params.to(dev, torch.float32).contiguous().clone()
-        if self.xgmi is not None:
-            self.grad = self.xgmi.buf[:self.master.numel()]
-            self.grad.zero_()
-        else:
-            self.grad = torch.zeros_like(self.master)
+        self.grad = self._flat_grad(self.master, always=True)
         bf = torch.bfloat16
         z = lambda *s, dt=bf: torch.zeros(*s, dtype=dt, device=dev)
         self.w1f, self.w2f, self.w2d = z(64, 96), z(64, 1600), z(64, 1600)
@@ -234,13 +199,8 @@ class FusedCifarEngine:
         self._fc_src = None
         self.loss_part = z(self.loss_parts, dt=torch.float32)
         self.correct_part = z(self.loss_parts, dt=torch.int32)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
-        # the head kernel copies the step counter here; the SGD (launch or in-launch) reads the copy,
-        # so one of its workgroups can bump step_t without an arrival ticket (cnn_sgd.hip)
-        self.step_sgd = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.ticket = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)   # two-level arrival counters
-        self.stats = torch.zeros(stats_len, 4, dtype=torch.float32, device=dev)
-        self.logits_buf = z(B, 10, dt=torch.float32)
+        # (step_sgd: the head kernel copies the step counter there; the SGD, launch or in-launch, reads
+        # the copy, so one of its workgroups can bump step_t without an arrival ticket, cnn_sgd.hip)
 
         p = {k: self.master[s.offset:s.offset + s.numel] for k, s in SEG.items()}
         self.pv = p
@@ -282,8 +242,6 @@ class FusedCifarEngine:
         self._dgrad_done = False
         self.bwd_hand = torch.zeros(self.bwd_hand_words, dtype=torch.int32, device=dev)
 
-        self.graphs: List[torch.cuda.CUDAGraph] = []
-        self.chains: Dict[int, Optional[torch.cuda.CUDAGraph]] = {}   # k -> graph of k chained steps
         self.comm_stream = torch.cuda.Stream(device=dev) if self.dp else None
         # N>1 step schedule: "overlap" = two buckets, fc all-reduce + fc SGD on the comm stream under
         # the conv backward; "serial" = one stream, one all-reduce of the whole flat gradient, one SGD
@@ -301,7 +259,6 @@ class FusedCifarEngine:
         # configuration does not have is an absent key.  Nothing rebinds these attributes afterwards
         # (evaluate() swaps data / labels only around eval forwards, which take them as arguments).
         self.buf = {k: t for k in BUF_NAMES if (t := getattr(self, k, None)) is not None}
-        self.host_step = 0
         self._sync_bidx()
         self.refresh_shadows()
 
@@ -318,9 +275,7 @@ class FusedCifarEngine:
         old = int(self.step_t.item())
         if (old ^ int(step)) & 1:      # the current fc1 shadow moves to the new step's parity slot
             self.fc1n[int(step) & 1].copy_(self.fc1n[old & 1])
-        self.step_t.fill_(int(step))
-        self.step_sgd.fill_(int(step))
-        self.host_step = int(step)
+        super().set_step(step)
         self._sync_bidx()
 
     def _sync_bidx(self):
@@ -333,24 +288,6 @@ class FusedCifarEngine:
         """The current step's raw images into xraw (the prefetching forward reads them there)."""
         if getattr(self, "xraw_prefetch", False):
             self.xraw.copy_(self.data.index_select(0, self.bidx.long()).view(self.B, 3072))
-
-    # --- data order ---------------------------------------------------------------------------
-    def epoch_permutation(self, epoch: int) -> torch.Tensor:
-        """This rank's dataset rows for ``epoch`` (int32 [period * Bv], batch after batch): the
-        generated order the kernels evaluate in place (data/order.py; D6: disjoint rank shards)."""
-        return self.order.epoch_shard(epoch).to(torch.int32)
-
-    def batch_indices(self, step: int) -> torch.Tensor:
-        """Dataset rows (int32 [Bv]) this rank trains on at global step ``step``."""
-        return self.order.batch(step).to(torch.int32)
-
-    def _padded(self, idx: torch.Tensor) -> torch.Tensor:
-        """An explicit index list of Bv rows padded to the kernel batch (last row repeated)."""
-        idx = idx.to(self.device, torch.int32).reshape(-1)
-        if idx.numel() == self.B:
-            return idx.contiguous()
-        assert 1 <= idx.numel() <= self.B, idx.numel()
-        return torch.cat([idx, idx[-1:].expand(self.B - idx.numel())]).contiguous()
 
     # --- kernels ------------------------------------------------------------------------------
     def _forward(self, idx, counter, period, train=True, logits_out=None):
@@ -456,10 +393,6 @@ class FusedCifarEngine:
                 self.part1, self.partb1, self.p1, self.dy2, self.part2, self.partb2, self.groups2, self.xraw,
                 **self._w8, **({"aug": self.aug} if self.aug is not None else {}))
 
-    def _sched(self, scale: float = 1.0) -> list:
-        """{lr0, decay, decay_steps, staircase, warmup, grad_scale} of the SGD ops and the fc chain."""
-        return [self.lr0, self.decay, self.decay_steps, 1.0 if self.staircase else 0.0, self.warmup, scale]
-
     def _prefetch_next(self, mode: int, finalize: bool = True) -> bool:
         """Whether an SGD of this mode also gathers the next step's raw images into xraw."""
         return bool(self.xraw_prefetch and mode in (0, 2) and finalize)
@@ -506,17 +439,6 @@ class FusedCifarEngine:
                 self.c12_flags.zero_()     # a timed-out hand-off can leave a partner's flag raised
             raise RuntimeError("; ".join(parts) + f" (blocks not co-resident, error word {e})")
 
-    def _allreduce(self, t: torch.Tensor):
-        import torch.distributed as dist
-        if t.dtype == torch.bfloat16:            # grad16: already on the wire's dtype
-            dist.all_reduce(t, group=self.pg)
-        elif self.comm_dtype == "bf16":
-            tb = t.to(torch.bfloat16)
-            dist.all_reduce(tb, group=self.pg)
-            t.copy_(tb)
-        else:
-            dist.all_reduce(t, group=self.pg)
-
     def _allreduce_bucket(self, fc: bool):
         off, n = self._buckets[fc]
         if self.xgmi is not None:
@@ -532,18 +454,6 @@ class FusedCifarEngine:
     def _wire_grad(self) -> torch.Tensor:
         """The flat gradient the collectives run on (grad16 on the RCCL bf16 wire)."""
         return self.grad16 if self.grad16 is not None else self.grad
-
-    def check_comm(self):
-        """Raise if the xGMI all-reduce saw a peer stop participating (sticky device error word) or a
-        wgrad sub-grid barrier timed out (device read: callers that must not sync use
-        ``check_barriers(cached=True)``)."""
-        self.check_barriers()
-        if self.xgmi is not None:
-            self.xgmi.check()
-
-    def _pg_backend(self) -> str:
-        import torch.distributed as dist
-        return dist.get_backend(self.pg) if dist.is_available() and dist.is_initialized() else "none"
 
     def _backend(self) -> str:
         if self.xgmi is not None:
@@ -658,11 +568,13 @@ class FusedCifarEngine:
             self._seg_compute_a()
             self._seg_compute_b()
             return
+        (self._serial_dp_step if self.dp_schedule == "serial" else self._dp_step)(self._segments())
+
+    def _segments(self):
+        """The data-parallel step's capturable pieces, between which its collectives run."""
         if self.dp_schedule == "serial":
-            self._serial_dp_step([self._seg_compute_ab, self._seg_apply])
-            return
-        self._dp_step([self._seg_forward, self._seg_fc, self._seg_compute_b_launch, self._seg_apply_fc,
-                       self._seg_apply_conv])
+            return [self._seg_compute_ab, self._seg_apply]
+        return [self._seg_forward, self._seg_fc, self._seg_compute_b_launch, self._seg_apply_fc, self._seg_apply_conv]
 
     def _seg_compute_ab(self):
         self._seg_compute_a()
@@ -727,44 +639,19 @@ class FusedCifarEngine:
             torch.cuda.current_stream(self.device).wait_event(ev)
             self._pending_comm = None
 
-    # --- graph capture --------------------------------------------------------------------------
-    @property
-    def single_graph(self) -> bool:
-        """The whole step (collectives included) is one capturable launch sequence."""
-        return not self.dp or self.capture_comm or self.xgmi is not None
+    # --- graph capture (capture / run / step: engine/base.py) --------------------------------------
+    def _replay_segments(self):
+        """RCCL without ``capture_comm``: the graphs of ``_segments`` around eager collectives."""
+        if self._captured_schedule == "serial":
+            self._serial_dp_step([g.replay for g in self.graphs])
+        else:
+            self._dp_step([g.replay for g in self.graphs])
+            self._join_comm()
 
     def capture(self, steps_per_graph: int = 8):
-        """Capture the step into HIP graph(s).  N=1, N>1 over xGMI and N>1 over RCCL with
-        ``capture_comm`` (the default): the whole step -- compute, all-reduce, SGD, on one or two
-        streams -- is one graph, and further graphs chain 2, 4, ... ``steps_per_graph`` complete
-        steps (every step reads its batch and LR through the device step counter, so consecutive
-        steps need no host work, across epoch boundaries too).  :meth:`run` replays any step count
-        as a sum of chains -- no single-step tails, no host gap between the chained steps.
-        RCCL without ``capture_comm``: compute graphs around eager collectives (no chains)."""
-        quiesce_for_capture(self.device, self.pg if self.dp else None)
-        self._reset_step_state()
-        self.graphs, self.chains = [], {}
-        pool = torch.cuda.graph_pool_handle()
-        if self.single_graph:
-            segs = [lambda: self._steps_joined(1)]
-        elif self.dp_schedule == "serial":
-            segs = [self._seg_compute_ab, self._seg_apply]
-        else:
-            segs = [self._seg_forward, self._seg_fc, self._seg_compute_b_launch, self._seg_apply_fc,
-                    self._seg_apply_conv]
         self._captured_schedule = self.dp_schedule
-        # a capture records launches without running them: the step counter and weights are
-        # identical before and after
-        for fn in segs:
-            self.graphs.append(self._capture_one(fn, pool))
-        if self.single_graph:
-            k = 2
-            while k <= int(steps_per_graph):
-                self.chains[k] = self._capture_one(lambda k=k: self._steps_joined(k), pool)
-                k *= 2
-        self.chains[1] = self.graphs[0] if self.single_graph else None
-        self._pool = pool
-        torch.cuda.synchronize(self.device)
+        super().capture(steps_per_graph)
+        self.chains.setdefault(1, None)    # (several graphs: no chains)
 
     def add_chain(self, k: int) -> bool:
         """Also capture a chain of exactly ``k`` steps, so :meth:`run` (k) is ONE graph replay (a
@@ -776,62 +663,6 @@ class FusedCifarEngine:
         self.chains[k] = self._capture_one(lambda: self._steps_joined(k), self._pool)
         torch.cuda.synchronize(self.device)
         return True
-
-    def _steps_joined(self, k: int):
-        """``k`` steps, then the comm stream joined (a captured graph must end on its origin stream;
-        inside it, step s's fc SGD overlaps step s+1's forward)."""
-        for _ in range(k):
-            self._eager_step()
-        self._join_comm()
-
-    def _capture_one(self, fn, pool):
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            # thread_local: the capture forbids unsafe calls on THIS thread only -- the process group's
-            # watchdog thread polls the events of earlier (eager) collectives, and under the default
-            # global mode one such poll invalidates the capture (seen on a 1-rank nccl group)
-            with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode="thread_local"):
-                fn()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        return g
-
-    @property
-    def multi(self):
-        """(k, graph) of the longest captured chain, or None."""
-        ks = [k for k, g in getattr(self, "chains", {}).items() if g is not None and k > 1]
-        return (max(ks), self.chains[max(ks)]) if ks else None
-
-    def run(self, n: int):
-        """``n`` complete training steps (asynchronous): the longest captured chains first, then the
-        binary decomposition of the remainder (e.g. 21 = 8 + 8 + 4 + 1 replays)."""
-        n = int(n)
-        chains = {k: g for k, g in getattr(self, "chains", {}).items() if g is not None}
-        if not self.graphs or not chains:
-            for _ in range(n):
-                self.step()
-            return
-        self._join_comm()
-        for k in sorted(chains, reverse=True):
-            while n >= k:
-                chains[k].replay()
-                self.host_step += k
-                n -= k
-
-    def step(self):
-        """One training step (asynchronous: returns once launched)."""
-        if not self.graphs:
-            self._eager_step()
-        elif len(self.graphs) == 1:
-            self._join_comm()
-            self.graphs[0].replay()
-        elif self._captured_schedule == "serial":
-            self._serial_dp_step([g.replay for g in self.graphs])
-        else:
-            self._dp_step([g.replay for g in self.graphs])
-            self._join_comm()
-        self.host_step += 1
 
     def tune_schedule(self, iters: int = 30, steps_per_graph: int = 8, rounds: int = 2, log=None) -> str:
         """Data-parallel step: capture each schedule (overlap / serial), time ``iters`` real
@@ -924,20 +755,9 @@ class FusedCifarEngine:
         return self.logits_buf[:n].clone()
 
     # --- state ----------------------------------------------------------------------------------
-    def read_stats(self, step: int) -> Dict[str, float]:
-        """Stats published by the SGD kernel for the step that produced global_step == ``step``."""
-        row = self.stats[(step - 1) % self.stats.shape[0]].tolist()
-        return {"global_step": int(row[0]), "loss": row[1], "accuracy": row[2], "lr": row[3]}
-
-    def global_step(self) -> int:
-        return int(self.step_t.item())
-
     def fc1n_current(self) -> torch.Tensor:
         """The bf16 fc1 weight shadow the kernels of the current step read ([2304][384])."""
         return self.fc1n[self.global_step() & 1]
-
-    def flat_params(self) -> torch.Tensor:
-        return self.master.detach().cpu()
 
     def load_flat_params(self, flat: torch.Tensor, step: Optional[int] = None):
         self.master.copy_(flat.to(self.device, torch.float32))

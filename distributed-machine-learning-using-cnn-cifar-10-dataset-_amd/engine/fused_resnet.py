@@ -19,61 +19,26 @@ all HIP kernels of csrc/kernels/resnet.hip, captured as one HIP graph:
 
 Batch statistics are per rank (as in the eager model under DP).  With data parallelism the SGD runs
 in two halves around ONE all-reduce of the 1.1 MB flat gradient (mode 1 -> RCCL -> mode 2).
+
+Which path a configuration takes and which layer reads which shortcut is decided by the pure function
+engine/plan_resnet.py plan_resnet_step; the constructor keeps the result as ``self.plan`` and
+allocates from it, and the per-layer launchers (_fwd, _dgrad, _bwd, _wgrad) read their wiring there.
+What this engine shares with the CNN engine (process fields, data order, graphs) is engine/base.py.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import torch
 
 from .. import config as C
-from ..parallel.dist import quiesce_for_capture
-from ..data.order import OrderSpec
 from ..models import resnet as R
-from ..ops import _ext
-from .fused import TICKET_WORDS
-
-OPS = None
-
-
-def _ops():
-    global OPS
-    if OPS is None:
-        _ext.hip()
-        OPS = torch.ops.dmlc
-    return OPS
-
-
-def layer_table():
-    """[(name prefix, cin, cout, hin, stride, shortcut mode used when this layer's output is applied)]
-    in execution order (l = 0..18)."""
-    layers = [("stem", 3, 16, 32, 1)]
-    cin, hin = 16, 32
-    for s, w in enumerate(R.WIDTHS):
-        for b in range(R.BLOCKS):
-            stride = 2 if (s > 0 and b == 0) else 1
-            layers.append((f"stage{s}/block{b}/a", cin, w, hin, stride))
-            hin //= stride
-            layers.append((f"stage{s}/block{b}/b", w, w, hin, 1))
-            cin = w
-    return layers
-
+from .base import FusedEngineBase
+from .plan_resnet import (LAYERS, NL, _block_sc_mode, _kp, _kpd, _pick_groups, layer_table,  # noqa: F401
+                          plan_resnet_step)
 
 NSLOT = 8            # BN statistics slots per layer (resnet.hip)
-LAYERS = layer_table()
-NL = len(LAYERS)
-assert NL == 19
-
-
-def _kp(cin):
-    return (9 * max(cin, 8) + 31) // 32 * 32
-
-
-def _kpd(cout):
-    return (9 * cout + 31) // 32 * 32
-
-
 FX_ONE = float(2 ** 48)   # fraction unit of the fixed-point BN statistics (resnet.hip fx_add)
 
 
@@ -93,15 +58,11 @@ def fx_decode(slots: torch.Tensor) -> torch.Tensor:
     return torch.where(bad, torch.full_like(tot, float("nan")), tot)
 
 
-def _block_sc_mode(b_layer: int) -> int:
-    """Shortcut mode of the block whose second conv is ``b_layer`` (1 identity, 2 subsample+pad)."""
-    a_layer = b_layer - 1
-    return 2 if LAYERS[a_layer][4] == 2 else 1
-
-
-class FusedResNetEngine:
+class FusedResNetEngine(FusedEngineBase):
     """Owns every device buffer of the fused ResNet-20 step.  Parameters: one flat fp32 buffer in the
     TF layout of models/resnet.py (HWIO kernels), BN moving statistics in a second flat buffer."""
+
+    _pick_groups = staticmethod(_pick_groups)
 
     def __init__(self, batch_size: int, data: torch.Tensor, labels: torch.Tensor, *, device=None,
                  flat_params: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
@@ -115,35 +76,19 @@ class FusedResNetEngine:
                  momentum: float = 0.0, weight_decay: float = 0.0, velocity: Optional[torch.Tensor] = None):
         if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
             raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
-        ops = _ops()
-        self.ops = ops
-        self.device = torch.device(device or "cuda")
-        dev = self.device
-        Bv = int(batch_size)
-        if Bv < 1:
-            raise ValueError("batch size must be >= 1")
-        # any batch size: the kernels run on the batch padded to the 16-image tile; the padding images
-        # are excluded from every BatchNorm statistic and get zero loss weight / gradient (nvalid)
-        B = -(-Bv // 16) * 16
-        self.B, self.Bv = B, Bv
-        self.world_size, self.rank, self.pg = world_size, rank, process_group
-        self.lr0, self.decay, self.decay_steps, self.staircase = lr, lr_decay, decay_steps, staircase
-        self.warmup = float(warmup_steps)      # linear LR warm-up, in the SGD kernel
-        self.seed, self.comm_dtype = seed, comm_dtype
-        self.dp = world_size > 1 or dp_force     # dp_force: the all-reduce path at world_size 1 (tests)
-        if capture_comm is None:                 # RCCL collectives inside the step graph (nccl only)
-            import torch.distributed as dist
-            nccl = dist.is_initialized() and dist.get_backend(process_group) == "nccl"
-            capture_comm = self.dp and nccl
-        self.capture_comm = bool(capture_comm)
-
-        assert data.dtype == torch.uint8 and tuple(data.shape[1:]) == (32, 32, 3)
-        self.data = data.to(dev).contiguous()
-        self.labels = labels.to(dev, torch.int32).contiguous()
-        self.n_data = self.data.shape[0]
-        self.order = OrderSpec(self.n_data, Bv, world_size, rank, seed)   # generated order (data/order.py)
-        self.period = self.order.period
-        self.order_desc = self.order.descriptor()
+        # every path decision and the layer wiring (engine/plan_resnet.py), then as plain attributes
+        self.plan = plan = plan_resnet_step(batch_size=batch_size, world_size=world_size, dp_force=dp_force,
+                                            groups=groups, wgrad_branch=wgrad_branch, merged_bwd=merged_bwd,
+                                            bwd_img_level=bwd_img_level, sgd_split=sgd_split)
+        super().__init__(device=device, world_size=world_size, rank=rank, process_group=process_group, seed=seed,
+                         comm_dtype=comm_dtype, lr=lr, lr_decay=lr_decay, decay_steps=decay_steps,
+                         staircase=staircase, warmup_steps=warmup_steps, dp_force=dp_force,
+                         capture_comm=capture_comm, stats_len=stats_len)
+        dev, B = self.device, plan.B
+        self._init_batch(data, labels, B, plan.Bv)
+        self.bwd_img_level, self.groups = int(bwd_img_level), list(plan.groups)
+        self.wgrad_branch, self.merged_bwd, self.sgd_split = plan.wgrad_branch, plan.merged_bwd, plan.sgd_split
+        self._sgd_points = plan.sgd_points
 
         f0, s0 = R.init_flat_params(torch.Generator().manual_seed(seed))
         if flat_params is not None:
@@ -160,19 +105,9 @@ class FusedResNetEngine:
         self.vel = torch.zeros_like(self.master) if self.momentum else None
         if velocity is not None and self.vel is not None:
             self.vel.copy_(velocity.to(dev, torch.float32))
-        # gradient all-reduce (N>1): xGMI peer-to-peer kernel over an IPC-shared buffer when it
-        # self-tests and measures faster than RCCL (parallel/xgmi.py), else RCCL
-        self.xgmi, self.comm_info = None, {"allreduce": "rccl" if self.dp else "none"}
-        if world_size > 1 and dev.type == "cuda" and comm_dtype in ("fp32", "bf16") and allreduce != "rccl":
-            from ..parallel import xgmi as X
-            self.xgmi, self.comm_info = X.select(self.master.numel(), rank, world_size, dev,
-                                                 [(0, self.master.numel())], mode=allreduce, group=process_group,
-                                                 wire=comm_dtype, captured=self.capture_comm)
-        if self.xgmi is not None:
-            self.grad = self.xgmi.buf[:self.master.numel()]
-            self.grad.zero_()
-        else:
-            self.grad = torch.zeros_like(self.master) if self.dp else None
+        # one all-reduce of the whole flat gradient per step
+        self._select_xgmi(self.master.numel(), [(0, self.master.numel())], allreduce)
+        self.grad = self._flat_grad(self.master, always=False)
         P = {s.name[len(R.SCOPE) + 1:]: s for s in R.PARAM_SPECS}
         S = {s.name[len(R.SCOPE) + 1:]: s for s in R.STATE_SPECS}
         view = lambda buf, s: buf[s.offset:s.offset + s.numel]
@@ -200,114 +135,66 @@ class FusedResNetEngine:
         # zeroed at the start of each forward
         self.acc = torch.zeros(2, NL, NSLOT, 256, dtype=torch.int64, device=dev)
         self.stat, self.red = self.acc[0], self.acc[1]
-        # per-image backward (k_rn_bwd_img, merged backward only): bwd_img_level 0 off, 1 the 16->16
-        # layers (their wgrad keeps one slab per image anyway), 2 also the 32->32 stride-1 layers (one
-        # slab per image instead of B/2 groups: more slab bytes for the SGD, fewer re-reads)
-        self.bwd_img_level = int(bwd_img_level)
-        self.groups = groups or [B if (self.bwd_img_level >= 2 and B <= 256 and (ci, co, h, s) == (32, 32, 16, 1))
-                                 else self._pick_groups(B, ci, co) for _, ci, co, h, s in LAYERS]
         self.part = [z(g, _kp(ci), co, dt=torch.float32) for g, (_, ci, co, _, _) in zip(self.groups, LAYERS)]
         self.fc_part = z(B, 656, dt=torch.float32)
         self.loss_img = z(B, dt=torch.float32)
         self.correct_img = z(B, dt=torch.int32)
-        self.logits_buf = z(B, 10, dt=torch.float32)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
-        # The SGD finds the last arriver with a ticket (the CNN engine's ticketless form -- the head
+        # (The SGD finds the last arriver with the ticket; the CNN engine's ticketless form -- the head
         # copies the step counter for the SGD -- measured no better here in r3: 0.679 / 0.682 ms vs
-        # 0.675 / 0.678 with the ticket); step_sgd is the kernel argument that form would use
-        self.step_sgd = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.ticket = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)   # two-level arrival counters
-        self.stats = torch.zeros(stats_len, 4, dtype=torch.float32, device=dev)
-
-        self.graphs: List[torch.cuda.CUDAGraph] = []
-        self.chains: Dict[int, torch.cuda.CUDAGraph] = {}
+        # 0.675 / 0.678 with the ticket; step_sgd is the kernel argument that form would use)
         if self.dp:
             self.comm_info.update(captured_comm=bool(self.capture_comm or self.xgmi is not None))
         self.side_stream = torch.cuda.Stream(device=dev)
-        # Backward schedule, measured per batch size (graph replay, img/s on 1 MI355X):
-        #                          B=256   B=1024
-        #   merged dgrad+wgrad     376 k   508 k   one launch per layer, no fork/join edges
-        #   two launches, 1 stream 363 k   590 k
-        #   wgrads on a branch     336 k   620 k   19 fork/join edges in the graph
-        # The merged kernel runs at the occupancy of the larger (wgrad) body, which costs more than the
-        # saved launches once each layer has >= ~4 dgrad workgroups per CU; wgrad_branch / merged_bwd
-        # override the choice.
-        self.wgrad_branch = (B > 256) if wgrad_branch is None else bool(wgrad_branch)
-        self.merged_bwd = (B <= 256) if merged_bwd is None else bool(merged_bwd)
-        # sgd_split=True (single GPU, merged backward): the SGD of stage 3 (layers 13-18) and of
-        # stage 2 (7-12) runs on a graph branch as soon as their weight gradients are complete, beside
-        # the stage-2 / stage-1 backward; the main-stream SGD does the rest and publishes the step.
-        # Measured at B=256: 341 k vs 371 k img/s with one SGD launch -- the co-resident SGD blocks
-        # slow the one-image-per-workgroup backward more than the hidden slab reads save: off.
-        self.sgd_split = bool(sgd_split) and not self.dp and self.merged_bwd and not self.wgrad_branch
-        self._sgd_points = {13: (13, NL), 7: (7, 13)}    # after bwd launch of layer l: SGD of [lo, hi)
-        self.host_step = 0
         self._stem_src = None          # explicit (idx, counter, period) of the stem wgrad, else generated
         self.refresh_shadows()
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _pick_groups(B: int, cin: int, cout: int) -> int:
-        """Split-K image groups of one wgrad (grid = groups x m-chunks): enough blocks to fill the chip
-        (256) while the fp32 slabs the SGD kernel reads back stay under 16 MB per layer (64 groups for
-        the 64-channel layers, 677 -> 667 us/step at B=256, profiles/r1_v17_rn_slab_cap_ab.txt).  A
-        power of two in [8, B]."""
-        blocks = 256
-        cap = 16.0 * 2 ** 20
-        mt = _kp(cin) // 16
-        mc = 1 if mt <= 12 else (2 if mt <= 24 else 3)      # Wg<>::MC in resnet.hip
-        lim = min(blocks / mc, cap / (_kp(cin) * cout * 4))
-        g = 1 << max(0, int(math.floor(math.log2(max(1.0, lim)))))
-        return int(max(1, min(B, max(8, g))))
-
     def refresh_shadows(self):
         self._sgd(mode=3)
-
-    def set_step(self, step: int):
-        self.step_t.fill_(int(step))
-        self.step_sgd.fill_(int(step))
-        self.host_step = int(step)
-
-    def epoch_permutation(self, epoch: int) -> torch.Tensor:
-        """This rank's rows of ``epoch`` (int32 [period * B]), the order the kernels generate."""
-        return self.order.epoch_shard(epoch).to(torch.int32)
 
     def bn_sums(self) -> torch.Tensor:
         """Decoded BatchNorm sums of the last step, fp64 [2, NL, 128]: [0] sum z / sum z^2, [1] R1 / R2
         (channels at [0, cout) and [64, 64 + cout))."""
         return fx_decode(self.acc)
 
-    def batch_indices(self, step: int) -> torch.Tensor:
-        return self.order.batch(step).to(torch.int32)
+    def _padded(self, idx: torch.Tensor) -> torch.Tensor:
+        """An explicit list of exactly Bv dataset rows, padded to the kernel batch."""
+        assert idx.numel() == self.Bv, (idx.numel(), self.Bv)
+        return super()._padded(idx)
 
-    # --- kernels ------------------------------------------------------------------------------
-    def _forward(self, idx, counter, period, logits_out=None):
-        o = self.ops
-        self.acc.zero_()
-        for l, (_, ci, co, h, s) in enumerate(LAYERS):
-            if l == 0:
-                o.rn_fwd(ci, co, h, s, self.data, idx, counter, period, 0, 0, None, None, None, None, None, 0, None,
-                         self.wf[0], self.z[0], self.stat[0], self.Bv)
-                continue
-            p = l - 1
-            sc_mode, sc_src = 0, None
-            if p >= 2 and p % 2 == 0:                  # layer p closes a residual block
-                sc_mode = _block_sc_mode(p)
-                sc_src = self.a[p - 2]
-            o.rn_fwd(ci, co, h, s, None, None, None, 1, 0, 0, self.z[p], self.stat[p], self.gamma[p], self.beta[p],
-                     sc_src, sc_mode, self.a[p], self.wf[l], self.z[l], self.stat[l], self.Bv)
-        o.rn_head(self.z[18], self.stat[18], self.gamma[18], self.beta[18], self.a[16], self.fcw, self.fcb,
-                  self.labels, idx, counter, period, 1.0 / (self.Bv * self.world_size), self.gy[18], self.red[18],
-                  self.fc_part, self.loss_img, self.correct_img, logits_out, self.Bv,
-                  self.step_t, self.step_sgd)
+    # --- kernels: one launcher per layer, wired by the plan --------------------------------------
+    def _fwd(self, l, src):
+        """conv_l with the BN-apply (+ shortcut) prologue of layer l - 1; ``src``: the batch's
+        (idx, counter, period), which only the stem reads."""
+        _, ci, co, h, s = LAYERS[l]
+        if l == 0:
+            idx, counter, period = src
+            self.ops.rn_fwd(ci, co, h, s, self.data, idx, counter, period, 0, 0, None, None, None, None, None, 0,
+                            None, self.wf[0], self.z[0], self.stat[0], self.Bv)
+            return
+        p = l - 1
+        sc_mode, sc = self.plan.fwd_sc[l]
+        self.ops.rn_fwd(ci, co, h, s, None, None, None, 1, 0, 0, self.z[p], self.stat[p], self.gamma[p],
+                        self.beta[p], None if sc is None else self.a[sc], sc_mode, self.a[p], self.wf[l], self.z[l],
+                        self.stat[l], self.Bv)
+
+    def _dgrad_args(self, l):
+        _, ci, co, h, s = LAYERS[l]
+        p = l - 1
+        sc_mode = self.plan.bwd_sc[l]
+        return (ci, co, h, s, self.gy[l], self.z[l], self.stat[l], self.red[l], self.gamma[l], self.wd[l], self.a[p],
+                self.z[p], self.stat[p], self.gy[l + 1] if sc_mode else None, sc_mode, self.gy[p], self.red[p])
+
+    def _dgrad(self, l):
+        self.ops.rn_dgrad(*self._dgrad_args(l), self.Bv)
+
+    def _bwd(self, l):
+        """dgrad_l and wgrad_l in one launch: both only read what dgrad_{l+1} produced."""
+        self.ops.rn_bwd(*self._dgrad_args(l), self.part[l], self.Bv, self.plan.per_image[l])
 
     def _per_image(self, l) -> bool:
-        """Layer l's dgrad and wgrad from one workgroup per image (k_rn_bwd_img): the 16->16 stride-1
-        layers whose weight gradient already keeps one split-K slab per image (G == B, B <= 256).
-        bwd_img_level=0: the merged launch with separate wgrad blocks."""
-        _, ci, co, h, s = LAYERS[l]
-        lvl = {(16, 16, 32, 1): 1, (32, 32, 16, 1): 2}.get((ci, co, h, s))
-        return bool(lvl and self.bwd_img_level >= lvl and self.part[l].shape[0] == self.B)
+        """Layer l's merged launch runs one workgroup per image (k_rn_bwd_img; plan_resnet.py)."""
+        return self.plan.per_image[l]
 
     def _wgrad(self, l):
         _, ci, co, h, s = LAYERS[l]
@@ -319,21 +206,21 @@ class FusedResNetEngine:
             self.ops.rn_wgrad(ci, co, h, s, None, None, None, 1, 0, 0, self.a[l - 1], self.gy[l], self.z[l],
                               self.stat[l], self.red[l], self.gamma[l], self.part[l], self.Bv)
 
+    def _forward(self, idx, counter, period, logits_out=None):
+        self.acc.zero_()
+        for l in range(NL):
+            self._fwd(l, (idx, counter, period))
+        self.ops.rn_head(self.z[18], self.stat[18], self.gamma[18], self.beta[18], self.a[16], self.fcw, self.fcb,
+                         self.labels, idx, counter, period, 1.0 / (self.Bv * self.world_size), self.gy[18],
+                         self.red[18], self.fc_part, self.loss_img, self.correct_img, logits_out, self.Bv,
+                         self.step_t, self.step_sgd)
+
     def _backward(self):
-        o = self.ops
         main = torch.cuda.current_stream(self.device)
         side = self.side_stream if self.wgrad_branch else main
         if side is main and self.merged_bwd:
-            # one launch per layer: dgrad_l and wgrad_l both only read what dgrad_{l+1} produced
             for l in range(NL - 1, 0, -1):
-                _, ci, co, h, s = LAYERS[l]
-                sc_mode, gy_sc = 0, None
-                if l % 2 == 1:
-                    sc_mode = _block_sc_mode(l + 1)
-                    gy_sc = self.gy[l + 1]
-                o.rn_bwd(ci, co, h, s, self.gy[l], self.z[l], self.stat[l], self.red[l], self.gamma[l], self.wd[l],
-                         self.a[l - 1], self.z[l - 1], self.stat[l - 1], gy_sc, sc_mode, self.gy[l - 1],
-                         self.red[l - 1], self.part[l], self.Bv, self._per_image(l))
+                self._bwd(l)
                 if self.sgd_split and l in self._sgd_points:
                     # layers >= l: slabs complete, weights no longer read this step
                     self.side_stream.wait_stream(main)
@@ -349,17 +236,8 @@ class FusedResNetEngine:
                 side.wait_event(ev)
             with torch.cuda.stream(side):
                 self._wgrad(l)
-            if l == 0:
-                break
-            _, ci, co, h, s = LAYERS[l]
-            p = l - 1
-            sc_mode, gy_sc = 0, None
-            if l % 2 == 1:                             # a-conv: its input also feeds the block shortcut
-                sc_mode = _block_sc_mode(l + 1)
-                gy_sc = self.gy[l + 1]
-            o.rn_dgrad(ci, co, h, s, self.gy[l], self.z[l], self.stat[l], self.red[l], self.gamma[l], self.wd[l],
-                       self.a[p], self.z[p], self.stat[p], gy_sc, sc_mode, self.gy[p], self.red[p],
-                       self.Bv)
+            if l > 0:
+                self._dgrad(l)
         if side is not main:
             main.wait_stream(side)
 
@@ -372,21 +250,10 @@ class FusedResNetEngine:
                         None, self.vel, self.momentum, self.weight_decay)
 
     def _allreduce(self, t: torch.Tensor):
-        import torch.distributed as dist
         if self.xgmi is not None:
             self.xgmi.all_reduce(0, t.numel())
-            return
-        if self.comm_dtype == "bf16":
-            tb = t.to(torch.bfloat16)
-            dist.all_reduce(tb, group=self.pg)
-            t.copy_(tb)
         else:
-            dist.all_reduce(t, group=self.pg)
-
-    def check_comm(self):
-        """Raise if the xGMI all-reduce saw a peer stop participating (sticky device error word)."""
-        if self.xgmi is not None:
-            self.xgmi.check()
+            super()._allreduce(t)
 
     def _seg_compute(self):
         self._forward(self.order_desc, self.step_t, self.period)
@@ -407,6 +274,15 @@ class FusedResNetEngine:
             self._allreduce(self.grad)
             self._seg_apply()
 
+    def _segments(self):
+        """RCCL without ``capture_comm``: compute and apply graphs around an eager all-reduce."""
+        return [self._seg_compute, self._seg_apply]
+
+    def _replay_segments(self):
+        self.graphs[0].replay()
+        self._allreduce(self.grad)
+        self.graphs[1].replay()
+
     def compute_gradients(self, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward + backward + slab reduction only (no update); the flat gradient lands in ``grad``.
         ``idx``: explicit dataset rows (int32 [B]) instead of this step's generated batch."""
@@ -426,66 +302,6 @@ class FusedResNetEngine:
         self._backward()
         self._sgd(mode=1)
         return self.grad
-
-    # --- graph capture --------------------------------------------------------------------------
-    @property
-    def single_graph(self) -> bool:
-        return not self.dp or self.capture_comm or self.xgmi is not None
-
-    def _capture_one(self, fn, pool):
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            # thread_local: the capture forbids unsafe calls on THIS thread only -- the process group's
-            # watchdog thread polls the events of earlier (eager) collectives, and under the default
-            # global mode one such poll invalidates the capture (seen on a 1-rank nccl group)
-            with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode="thread_local"):
-                fn()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        return g
-
-    def capture(self, steps_per_graph: int = 8):
-        """The whole step as one graph (N=1, xGMI, or RCCL with ``capture_comm``) plus chains of
-        2, 4, ... ``steps_per_graph`` steps for :meth:`run`; RCCL without ``capture_comm``: compute
-        and apply graphs around an eager all-reduce."""
-        quiesce_for_capture(self.device, self.pg if self.dp else None)
-        self.graphs, self.chains = [], {}
-        pool = torch.cuda.graph_pool_handle()
-        segs = [self._eager_step] if self.single_graph else [self._seg_compute, self._seg_apply]
-        for fn in segs:
-            self.graphs.append(self._capture_one(fn, pool))
-        if self.single_graph:
-            self.chains[1] = self.graphs[0]
-            k = 2
-            while k <= int(steps_per_graph):
-                self.chains[k] = self._capture_one(lambda k=k: [self._eager_step() for _ in range(k)], pool)
-                k *= 2
-        torch.cuda.synchronize(self.device)
-
-    def run(self, n: int):
-        """``n`` training steps: longest chains first, then the binary decomposition of the rest."""
-        n = int(n)
-        if not self.chains:
-            for _ in range(n):
-                self.step()
-            return
-        for k in sorted(self.chains, reverse=True):
-            while n >= k:
-                self.chains[k].replay()
-                self.host_step += k
-                n -= k
-
-    def step(self):
-        if not self.graphs:
-            self._eager_step()
-        elif len(self.graphs) == 1:
-            self.graphs[0].replay()
-        else:
-            self.graphs[0].replay()
-            self._allreduce(self.grad)
-            self.graphs[1].replay()
-        self.host_step += 1
 
     # --- evaluation -----------------------------------------------------------------------------
     def eval_model(self):
@@ -510,14 +326,6 @@ class FusedResNetEngine:
             total += y.numel()
         return correct / max(1, total)
 
-    def _padded(self, idx: torch.Tensor) -> torch.Tensor:
-        """An explicit list of Bv dataset rows, padded to the kernel batch (last row repeated)."""
-        idx = idx.to(self.device, torch.int32).reshape(-1)
-        assert idx.numel() == self.Bv, (idx.numel(), self.Bv)
-        if self.Bv == self.B:
-            return idx.contiguous()
-        return torch.cat([idx, idx[-1:].expand(self.B - self.Bv)]).contiguous()
-
     @torch.no_grad()
     def forward_logits(self, idx: torch.Tensor) -> torch.Tensor:
         """Train-mode (batch statistics) logits of the Bv dataset rows ``idx`` via the fused kernels —
@@ -526,16 +334,6 @@ class FusedResNetEngine:
         return self.logits_buf[:self.Bv].clone()
 
     # --- state ----------------------------------------------------------------------------------
-    def read_stats(self, step: int) -> Dict[str, float]:
-        row = self.stats[(step - 1) % self.stats.shape[0]].tolist()
-        return {"global_step": int(row[0]), "loss": row[1], "accuracy": row[2], "lr": row[3]}
-
-    def global_step(self) -> int:
-        return int(self.step_t.item())
-
-    def flat_params(self) -> torch.Tensor:
-        return self.master.detach().cpu()
-
     def velocity_params(self) -> Optional[torch.Tensor]:
         """The momentum velocity in the layout of :meth:`flat_params` (CPU copy); None without momentum."""
         return None if self.vel is None else self.vel.detach().cpu()

@@ -46,6 +46,7 @@ class CommFailure(RuntimeError):
 class _FusedAdapter:
     kind = "fused"
     TUNE_ITERS = 20
+    tunes_schedule = True     # --dp_schedule=auto times the engine's two data-parallel schedules
 
     def __init__(self, cfg: C.TrainConfig, info: D.DistInfo, data, labels):
         if cfg.momentum or cfg.weight_decay:
@@ -74,7 +75,7 @@ class _FusedAdapter:
         self.eng.step()
         self.eng.capture(self.cfg.steps_per_graph)
         windows = 4 * (self.TUNE_ITERS + self.cfg.steps_per_graph)
-        if (self.cfg.dp_schedule == "auto" and self.eng.dp and hasattr(self.eng, "tune_schedule")
+        if (self.cfg.dp_schedule == "auto" and self.eng.dp and self.tunes_schedule
                 and self.cfg.generations - self.global_step >= 10 * windows):
             self.eng.tune_schedule(iters=self.TUNE_ITERS, steps_per_graph=self.cfg.steps_per_graph, log=log)
 
@@ -91,8 +92,7 @@ class _FusedAdapter:
 
     def device_event(self):
         # the wgrad barrier error word rides along with every chunk (pinned copy, no sync)
-        if hasattr(self.eng, "queue_error_copy"):
-            self.eng.queue_error_copy()
+        self.eng.queue_error_copy()
         ev = torch.cuda.Event()
         ev.record()
         return ev
@@ -100,14 +100,18 @@ class _FusedAdapter:
     def check_comm(self):
         # a timed-out wgrad sub-grid barrier is not a peer failure (a restart would repeat it): a plain
         # RuntimeError, raised before anything (e.g. a checkpoint) can use the step's weights
-        # (the engine's message names the kernel whose wait timed out and the switch that turns it off)
-        if hasattr(self.eng, "check_barriers"):
-            self.eng.check_barriers(cached=True)
+        # (the engine's message names the kernel whose wait timed out and the switch that turns it off);
+        # the pinned copy, not the engine's check_comm(): its device read would wait for the chunk in flight
+        self.eng.check_barriers(cached=True)
         try:
-            if getattr(self.eng, "xgmi", None) is not None:
+            if self.eng.xgmi is not None:
                 self.eng.xgmi.check()
         except RuntimeError as e:
             raise CommFailure(str(e)) from e
+
+    @property
+    def comm_info(self) -> dict:
+        return self.eng.comm_info     # the all-reduce this run actually uses (xgmi / rccl ...)
 
     @property
     def global_step(self) -> int:
@@ -115,10 +119,9 @@ class _FusedAdapter:
 
     def stats(self) -> Dict[str, float]:
         st = self.eng.read_stats(self.eng.host_step)     # (a device sync: the error word is current too)
-        if hasattr(self.eng, "check_barriers"):
-            # a persistent launch's wait that timed out (its blocks were not co-resident) leaves wrong
-            # weights: stop loudly (the message names the kernel and its off switch)
-            self.eng.check_barriers()
+        # a persistent launch's wait that timed out (its blocks were not co-resident) leaves wrong
+        # weights: stop loudly (the message names the kernel and its off switch)
+        self.eng.check_barriers()
         return st
 
     def tf_tensors(self) -> Dict[str, torch.Tensor]:
@@ -152,6 +155,7 @@ class _FusedAdapter:
 class _FusedResNetAdapter(_FusedAdapter):
     """ResNet-20 on the fused HIP engine (engine/fused_resnet.py): parameters + BN moving statistics
     checkpointed under the same names as the eager model."""
+    tunes_schedule = False    # one data-parallel schedule
 
     def __init__(self, cfg: C.TrainConfig, info: D.DistInfo, data, labels):
         from .fused_resnet import FusedResNetEngine
@@ -202,6 +206,7 @@ def _restored_velocity(tensors, specs, flat_size: int) -> torch.Tensor:
 
 class _EagerAdapter:
     kind = "eager"
+    comm_info: dict = {}      # (torch's own all-reduce: the process group's backend)
 
     def __init__(self, cfg: C.TrainConfig, info: D.DistInfo, data, labels, backend: str = "torch"):
         from .eager import EagerTrainer
@@ -399,12 +404,11 @@ class Session:
         self.engine.check_comm()
 
     def _allreduce_path(self) -> str:
-        info = getattr(getattr(self.engine, "eng", None), "comm_info", None) or {}
-        return str(info.get("allreduce", self.info.backend))
+        return str(self.engine.comm_info.get("allreduce", self.info.backend))
 
     def _check_replicas(self):
         """Every synchronous replica must hold bit-identical parameters (parallel/health.py)."""
-        if self.info.world_size <= 1 or not self.cfg.check_replicas or not hasattr(self.engine, "param_checksum"):
+        if self.info.world_size <= 1 or not self.cfg.check_replicas:
             return
         cs = self.engine.param_checksum()
         dev = self.info.device if self.info.backend == "nccl" else torch.device("cpu")

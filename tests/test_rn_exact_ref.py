@@ -249,15 +249,11 @@ def test_gpu_cases_meet_their_preconditions(case):
 
 def test_gpu_pair_tables_equal_the_engines_layers():
     """The (geometry, shortcut mode) pairs of the GPU tests are exactly those the engine launches: the
-    rules of FusedResNetEngine._forward (layer l applies BN_{l-1}; an even l - 1 >= 2 closes a block) and
-    _backward (an odd l feeds the shortcut of the block it opens)."""
-    fwd, bwd = set(), set()
-    for l, (_, ci, co, h, s) in enumerate(E.LAYERS):
-        p = l - 1
-        mode = E._block_sc_mode(p) if (l > 0 and p >= 2 and p % 2 == 0) else 0
-        fwd.add(((ci, co, h, s), mode))
-        if l > 0:
-            bwd.add(((ci, co, h, s), E._block_sc_mode(l + 1) if l % 2 == 1 else 0))
+    wiring its per-layer launchers read from the plan (engine/plan_resnet.py fwd_sc / bwd_sc)."""
+    from dmlc.engine.plan_resnet import plan_resnet_step
+    plan = plan_resnet_step(batch_size=16)
+    fwd = {(tuple(L[1:5]), plan.fwd_sc[l][0]) for l, L in enumerate(E.LAYERS)}
+    bwd = {(tuple(L[1:5]), plan.bwd_sc[l]) for l, L in enumerate(E.LAYERS) if l > 0}
     assert fwd == set(X.FWD_PAIRS) and len(X.FWD_PAIRS) == len(fwd) == 11
     assert bwd == set(X.BWD_PAIRS) and len(X.BWD_PAIRS) == len(bwd) == 8
     assert {tuple(L[1:5]) for L in E.LAYERS} == set(X.GEOMS)

@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import dmlc  # noqa: E402,F401
-from dmlc.engine.fused_resnet import FusedResNetEngine, LAYERS, _block_sc_mode  # noqa: E402
+from dmlc.engine.fused_resnet import NL, FusedResNetEngine  # noqa: E402
 
 
 def timeit(fn, iters):
@@ -44,25 +44,12 @@ def main():
     torch.cuda.synchronize()
     o = eng.ops
     res = {"variant": os.environ.get("DMLC_VARIANT", ""), "batch": a.batch}
-    for l, (_, ci, co, h, s) in enumerate(LAYERS):
-        if l == 0:
-            f = lambda: o.rn_fwd(ci, co, h, s, eng.data, eng.order_desc, eng.step_t, eng.period, 0, 0, None, None, None,
-                                 None, None, 0, None, eng.wf[0], eng.z[0], eng.stat[0])
-        else:
-            p = l - 1
-            scm, scs = (_block_sc_mode(p), eng.a[p - 2]) if (p >= 2 and p % 2 == 0) else (0, None)
-            f = (lambda l=l, p=p, ci=ci, co=co, h=h, s=s, scm=scm, scs=scs:
-                 o.rn_fwd(ci, co, h, s, None, None, None, 1, 0, 0, eng.z[p], eng.stat[p], eng.gamma[p], eng.beta[p],
-                          scs, scm, eng.a[p], eng.wf[l], eng.z[l], eng.stat[l]))
-        res[f"fwd{l}"] = timeit(f, a.iters)
-        res[f"wgrad{l}"] = timeit(lambda l=l: eng._wgrad(l), a.iters)
+    src = (eng.order_desc, eng.step_t, eng.period)
+    for l in range(NL):                  # the engine's own per-layer launchers (wired by eng.plan)
+        res[f"fwd{l}"] = timeit(lambda: eng._fwd(l, src), a.iters)
+        res[f"wgrad{l}"] = timeit(lambda: eng._wgrad(l), a.iters)
         if l > 0:
-            p = l - 1
-            scm, gsc = (_block_sc_mode(l + 1), eng.gy[l + 1]) if l % 2 == 1 else (0, None)
-            res[f"dgrad{l}"] = timeit(
-                lambda l=l, p=p, ci=ci, co=co, h=h, s=s, scm=scm, gsc=gsc:
-                o.rn_dgrad(ci, co, h, s, eng.gy[l], eng.z[l], eng.stat[l], eng.red[l], eng.gamma[l], eng.wd[l],
-                           eng.a[p], eng.z[p], eng.stat[p], gsc, scm, eng.gy[p], eng.red[p]), a.iters)
+            res[f"dgrad{l}"] = timeit(lambda: eng._dgrad(l), a.iters)
     res["head"] = timeit(lambda: o.rn_head(eng.z[18], eng.stat[18], eng.gamma[18], eng.beta[18], eng.a[16], eng.fcw,
                                            eng.fcb, eng.labels, eng.order_desc, eng.step_t, eng.period, 1.0 / eng.B,
                                            eng.gy[18], eng.red[18], eng.fc_part, eng.loss_img, eng.correct_img,
