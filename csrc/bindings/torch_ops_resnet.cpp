@@ -1,4 +1,5 @@
-// torch.ops.dmlc.rn_* bindings of the fused ResNet-20 kernels (csrc/kernels/resnet.hip, resnet_head.hip, resnet_sgd.hip).
+// torch.ops.dmlc.rn_* bindings of the fused ResNet-20 kernels (csrc/kernels/resnet.hip, resnet_head.hip,
+// resnet_sgd.hip, resnet_infer.hip).
 //
 // Same contract as torch_ops.cpp: every launch is preceded by a full check of device, dtype,
 // contiguity and the exact shapes implied by the layer geometry (one of the six ResNet-20 conv
@@ -342,9 +343,81 @@ void rn_sgd(const Tensor& master, const c10::optional<Tensor>& grad, double grad
   CHECK_HIP(dmlc_rn_sgd(&a, stream_of(master)));
 }
 
+// Whole-network eval-mode inference: image i is data[idx[i]] (idx None: data[i], N = data rows); one
+// launch writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels, one per data row)
+void rn_infer(const Tensor& data, const c10::optional<Tensor>& idx, const c10::optional<Tensor>& labels,
+              at::TensorList wf, const Tensor& master, const Tensor& state, at::IntArrayRef gamma_off,
+              at::IntArrayRef beta_off, at::IntArrayRef mm_off, at::IntArrayRef mv_off, int64_t fcw_off,
+              int64_t fcb_off, const Tensor& logits, const c10::optional<Tensor>& pred,
+              const c10::optional<Tensor>& correct, int64_t blocks) {
+  constexpr int L = DMLC_RN_LAYERS;
+  check_data(data);
+  const int64_t rows = data.size(0), N = idx.has_value() ? idx->numel() : rows;
+  TORCH_CHECK(rows >= 1 && rows < (1ll << 31), "rn_infer: 1 <= data rows < 2^31");
+  TORCH_CHECK(N >= 1 && N < (1ll << 31) / 10, "rn_infer: 1 <= N < 2^31 / 10");
+  TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "rn_infer: blocks must be >= 0 (0: the default grid)");
+  TORCH_CHECK(gamma_off.size() == L && beta_off.size() == L && mm_off.size() == L && mv_off.size() == L,
+              "rn_infer: 19 offsets per table");
+  TORCH_CHECK(wf.size() == L, "rn_infer: 19 forward shadows");
+  dev(master, "master"); dev(state, "state");
+  TORCH_CHECK(master.scalar_type() == at::kFloat && state.scalar_type() == at::kFloat, "master/state must be fp32");
+  const int64_t np = master.numel(), ns = state.numel();
+  TORCH_CHECK(fcw_off >= 0 && fcw_off + 640 <= np && fcb_off >= 0 && fcb_off + 10 <= np, "bad fc offsets");
+  const auto same_dev = [&](const Tensor& t, const char* n) {
+    TORCH_CHECK(t.device() == data.device(), "rn_infer: ", n, " must be on data's device");
+  };
+  same_dev(master, "master"); same_dev(state, "state");
+  DmlcRnInferArgs a{};
+  a.data = data.data_ptr<uint8_t>(); a.nrows = (int)rows;
+  if (idx.has_value()) {
+    check_numel(*idx, "idx", at::kInt, N);
+    same_dev(*idx, "idx");
+    a.idx = idx->data_ptr<int>();
+  }
+  if (labels.has_value()) {
+    check_numel(*labels, "labels", at::kInt, rows);
+    same_dev(*labels, "labels");
+    a.labels = labels->data_ptr<int>();
+  }
+  for (int l = 0; l < L; ++l) {
+    const Geom g = geom(kLayers[l][0], kLayers[l][1], kLayers[l][2], kLayers[l][3]);
+    check(wf[l], "wf", at::kBFloat16, {g.cout, g.kp()});
+    same_dev(wf[l], "wf");
+    TORCH_CHECK(gamma_off[l] >= 0 && gamma_off[l] + g.cout <= np && beta_off[l] >= 0 && beta_off[l] + g.cout <= np,
+                "bad BN offset ", l);
+    TORCH_CHECK(mm_off[l] >= 0 && mm_off[l] + g.cout <= ns && mv_off[l] >= 0 && mv_off[l] + g.cout <= ns,
+                "bad BN state offset ", l);
+    a.wf[l] = wf[l].data_ptr();
+    a.gamma_off[l] = (int)gamma_off[l]; a.beta_off[l] = (int)beta_off[l];
+    a.mm_off[l] = (int)mm_off[l]; a.mv_off[l] = (int)mv_off[l];
+  }
+  a.master = master.data_ptr<float>(); a.state = state.data_ptr<float>();
+  a.fcw_off = (int)fcw_off; a.fcb_off = (int)fcb_off;
+  check(logits, "logits", at::kFloat, {N, 10});
+  same_dev(logits, "logits");
+  a.logits = logits.data_ptr<float>();
+  if (pred.has_value()) {
+    check_numel(*pred, "pred", at::kInt, N);
+    same_dev(*pred, "pred");
+    a.pred = pred->data_ptr<int>();
+  }
+  if (correct.has_value()) {
+    TORCH_CHECK(labels.has_value(), "rn_infer: correct needs labels");
+    check_numel(*correct, "correct", at::kInt, N);
+    same_dev(*correct, "correct");
+    a.correct = correct->data_ptr<int>();
+  }
+  a.N = (int)N; a.blocks = (int)blocks;
+  c10::DeviceGuard guard(data.device());
+  CHECK_HIP(dmlc_rn_infer(&a, stream_of(data)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(dmlc, m) {
+  m.def("rn_infer(Tensor data, Tensor? idx, Tensor? labels, Tensor[] wf, Tensor master, Tensor state, "
+        "int[] gamma_off, int[] beta_off, int[] mm_off, int[] mv_off, int fcw_off, int fcb_off, "
+        "Tensor(a!) logits, Tensor(b!)? pred, Tensor(c!)? correct, int blocks=0) -> ()");
   m.def("rn_fwd(int cin, int cout, int hin, int stride, Tensor? data, Tensor? idx, Tensor? counter, int period, "
         "int cy, int cx, Tensor? z_prev, Tensor? stat_prev, Tensor? gamma_prev, Tensor? beta_prev, Tensor? sc_src, "
         "int sc_mode, Tensor(a!)? a_out, Tensor w, Tensor(b!) z, Tensor(c!) stat, "
@@ -379,4 +452,5 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("rn_bwd", &rn_bwd);
   m.impl("rn_head", &rn_head);
   m.impl("rn_sgd", &rn_sgd);
+  m.impl("rn_infer", &rn_infer);
 }

@@ -111,6 +111,27 @@ struct DmlcRnSgdArgs {
   int nvalid;                // valid images of the batch (loss / accuracy means)
 };
 
+// Whole-network eval-mode inference (resnet_infer.hip): uint8 pixels -> logits in one launch, one
+// workgroup per image in a persistent loop.  Image i is dataset row idx[i] (idx == nullptr: row i),
+// clamped to [0, nrows).  BatchNorm is the affine map of the moving statistics in `state`; the convs
+// read the forward shadows the SGD kernel keeps current.  Writes logits (and pred / correct) only.
+struct DmlcRnInferArgs {
+  const uint8_t* data; int nrows;       // uint8 [nrows][32][32][3]
+  const int* idx;                       // nullable int32 [N]
+  const int* labels;                    // nullable int32 [nrows] (required by `correct`)
+  const void* wf[DMLC_RN_LAYERS];       // bf16 [COUT][KP] forward shadows
+  const float* master; const float* state;
+  int gamma_off[DMLC_RN_LAYERS], beta_off[DMLC_RN_LAYERS];   // into master
+  int mm_off[DMLC_RN_LAYERS], mv_off[DMLC_RN_LAYERS];        // into state
+  int fcw_off, fcb_off;
+  float* logits;                        // fp32 [N][10]
+  int* pred;                            // nullable int32 [N]: first maximum of the logits
+  int* correct;                         // nullable int32 [N]: pred == labels[row]
+  int N;
+  int blocks;                           // workgroups (0: LDS-limited workgroups per CU x CUs), capped at N
+};
+
+hipError_t dmlc_rn_infer(const DmlcRnInferArgs* a, hipStream_t s);
 hipError_t dmlc_rn_fwd(const DmlcRnLayerGeom* g, const DmlcRnFwdArgs* a, hipStream_t s);
 hipError_t dmlc_rn_dgrad(const DmlcRnLayerGeom* g, const DmlcRnDgradArgs* a, hipStream_t s);
 hipError_t dmlc_rn_wgrad(const DmlcRnLayerGeom* g, const DmlcRnWgradArgs* a, hipStream_t s);

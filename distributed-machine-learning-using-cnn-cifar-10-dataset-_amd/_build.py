@@ -38,6 +38,9 @@ VARIANT, VARIANT_FLAGS = (_VAR.split(":", 1)[0], _VAR.split(":", 1)[1].split()) 
 _SUFFIX = "_timing" if TIMING else (f"_{VARIANT}" if VARIANT else "")
 HIP_LIB = os.path.join(LIB_DIR, f"libdmlc_hip{_SUFFIX}.so")
 RT_LIB = os.path.join(LIB_DIR, "_dmlc_rt" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
+# extra hipcc flags of single kernel files.  resnet_infer.hip: scalar fp32 VALU only (no packed fp32
+# pairs), so an image's logits cannot depend on how the compiler paired the epilogue's values
+HIP_FILE_FLAGS = {"resnet_infer.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_paths():
@@ -116,7 +119,7 @@ def build(hip: bool = True, rt: bool = True, jobs: int | None = None) -> dict:
         for src in sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip"))):
             o = os.path.join(OBJ_DIR, os.path.basename(src) + (f"{_SUFFIX.replace('_', '.')}.o" if _SUFFIX else ".o"))
             hip_objs.append(o)
-            jobs_list.append((src, headers, o, [hipcc], hip_flags))
+            jobs_list.append((src, headers, o, [hipcc], hip_flags + HIP_FILE_FLAGS.get(os.path.basename(src), [])))
         bheaders = headers + glob.glob(os.path.join(CSRC, "bindings", "*.h"))
         for bsrc in sorted(glob.glob(os.path.join(CSRC, "bindings", "*.cpp"))):
             o = os.path.join(OBJ_DIR, os.path.basename(bsrc) + ".o")

@@ -17,6 +17,10 @@ all HIP kernels of csrc/kernels/resnet.hip, captured as one HIP graph:
                  + bf16 weight shadows + global_step++ + stats ring; with ``momentum`` /
                  ``weight_decay`` the same kernel keeps the velocity and adds the L2 term
 
+Evaluation and inference (``evaluate``, ``infer``, ``infer_logits``) are one launch of k_rn_infer
+(csrc/kernels/resnet_infer.hip): the whole eval-mode network per image in one workgroup, activations in
+LDS, reading the same bf16 forward shadows, master and state the step keeps current.
+
 Batch statistics are per rank (as in the eager model under DP).  With data parallelism the SGD runs
 in two halves around ONE all-reduce of the 1.1 MB flat gradient (mode 1 -> RCCL -> mode 2).
 
@@ -311,10 +315,51 @@ class FusedResNetEngine(FusedEngineBase):
         return m
 
     @torch.no_grad()
-    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0) -> float:
-        """Test accuracy with the BN moving statistics (eval-mode forward of the same weights)."""
-        m = self.eval_model()
+    def infer(self, images_u8: torch.Tensor, labels: Optional[torch.Tensor] = None,
+              idx: Optional[torch.Tensor] = None, blocks: Optional[int] = None):
+        """Eval-mode forward (BN moving statistics) of any uint8 [N,32,32,3] images in ONE launch of
+        k_rn_infer (csrc/kernels/resnet_infer.hip): (logits fp32 [n,10], pred int32 [n], correct int32 [n]
+        or None without ``labels``).  ``idx``: rows of ``images_u8`` to run (n = len(idx)), else all of them;
+        ``labels``: one per row of ``images_u8``; ``blocks``: workgroups of the persistent loop (None: as
+        many as the chip holds).  Reads the weights as the last step left them; writes no training buffer."""
+        dev = self.device
+        assert images_u8.dtype == torch.uint8 and tuple(images_u8.shape[1:]) == (32, 32, 3), images_u8.shape
+        images_u8 = images_u8.to(dev).contiguous()
+        if idx is not None:
+            idx = idx.to(dev, torch.int32).reshape(-1).contiguous()
+        n = images_u8.shape[0] if idx is None else idx.numel()
+        if labels is not None:
+            labels = labels.to(dev, torch.int32).reshape(-1).contiguous()
+        logits = torch.empty(n, 10, dtype=torch.float32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        correct = None if labels is None else torch.empty(n, dtype=torch.int32, device=dev)
+        self.ops.rn_infer(images_u8, idx, labels, self.wf, self.master, self.state, self.gamma_off, self.beta_off,
+                          self.mm_off, self.mv_off, self.fcw_off, self.fcb_off, logits, pred, correct,
+                          int(blocks or 0))
+        return logits, pred, correct
+
+    def infer_logits(self, images_u8: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                     blocks: Optional[int] = None) -> torch.Tensor:
+        """Eval-mode logits fp32 [n,10] of uint8 images (see :meth:`infer`)."""
+        return self.infer(images_u8, None, idx, blocks)[0]
+
+    @torch.no_grad()
+    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0, impl: str = "hip") -> float:
+        """Test accuracy with the BN moving statistics (eval-mode forward of the same weights).
+        ``impl="hip"``: the first ``max_batches * batch`` images (0: all) through k_rn_infer in one launch,
+        the hits summed on the device; ``impl="torch"``: the fp32 PyTorch model of :meth:`eval_model`,
+        batch by batch."""
+        if impl not in ("hip", "torch"):
+            raise ValueError(f"evaluate: impl must be 'hip' or 'torch', got {impl!r}")
         n = data.shape[0]
+        if impl == "hip":
+            if max_batches:
+                n = min(n, max_batches * self.Bv)
+            if n == 0:
+                return 0.0
+            correct = self.infer(data[:n], labels[:n])[2]
+            return int(correct.sum()) / n
+        m = self.eval_model()
         nb = math.ceil(n / self.Bv)
         if max_batches:
             nb = min(nb, max_batches)
