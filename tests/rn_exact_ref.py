@@ -19,6 +19,9 @@ the oracle's integer sums and every fraction word is zero.
 Layouts: activations NHWC, weights HWIO (models/resnet.py).  Every function computes in fp64 and takes
 real inputs too (the CPU tests compare them with autograd on random reals); ``_int`` asserts that a
 result is an integer tensor.
+
+The second half of the file is the oracle of the whole-network inference kernel (resnet_infer.hip):
+``infer_exact``, ``make_infer_case`` and ``infer_buffers``; see the comment that opens it.
 """
 import functools
 import types
@@ -63,10 +66,10 @@ def _pad_before(stride):
     return 1 if stride == 1 else 0
 
 
-def _xpad(x, stride):
+def _xpad(x, stride, fill=0.0):
     B, H, W, C = x.shape
     pb = _pad_before(stride)
-    out = torch.zeros(B, H + pb + 1, W + pb + 1, C, dtype=F64)
+    out = torch.full((B, H + pb + 1, W + pb + 1, C), fill, dtype=F64)
     out[:, pb:pb + H, pb:pb + W, :] = x
     return out
 
@@ -546,3 +549,332 @@ GPU_CASES = (tuple(("fwd", g, 1, 16, 16, m) for g, m in FWD_PAIRS)
              + tuple(("bwd", g, 3, 16, 16, m) for g, m in BWD_PAIRS) + (("bwd", STEM, 3, 16, 16, 0),)
              + (("bwd", S32, 4, 16, 8, 1), ("bwd", D32, 4, 16, 8, 2))
              + (("head", None, 22, 16, 16, 0), ("head", None, 22, 16, 8, 0)))
+
+
+# ==================================================================================================
+# Whole-network eval-mode inference (csrc/kernels/resnet_infer.hip k_rn_infer): all 19 convolutions,
+# the 9 residual adds and the head of ONE launch, from uint8 pixels to logits.
+#
+# Why it is exact: pixels are integers bf16 holds; the kernel folds BatchNorm in fp32 as
+# sc = gamma * (1 / sqrtf(mv + 1e-3f)), sh = beta - mm * sc, and mv = float32(4^k - 1e-3) makes
+# mv + eps == 4^k in fp32, so sc = gamma 2^-k and, with integer gamma, beta and mm, sh are exact.
+# Activations are rounded to bf16 (nearest even) only where the kernel stores an operand: the input,
+# each a-conv output, each block output; the last layer stays fp32 into the pool.  The oracle rounds
+# at the same places, so stored values need NOT be bf16 integers.  What must hold is that every fp32
+# sum of the kernel is exact in any order (MFMA sums, acc * sc + sh (+ shortcut), the 64-term pool sum,
+# the 64-term fc sum): all terms of a sum are multiples of one power of two q and sum |terms| <
+# 2^24 q, so every partial sum is m q with |m| < 2^24.  infer_exact asserts this per output element
+# and names the layer.
+INF_GEOM = (STEM,) + (S16,) * 6 + (D32,) + (S32,) * 5 + (D64,) + (S64,) * 5
+INF_SC = (0, 0, 1, 0, 1, 0, 1, 0, 2, 0, 1, 0, 1, 0, 2, 0, 1, 0, 1)       # shortcut mode of each layer's epilogue
+INF_LAYERS = 19
+_BIG = 1000                                                              # log2 granule of an exact zero
+
+
+def infer_layer_id(l):
+    """'l08-s1b0b-32x32x16s1-sc2': layer, stage / block / conv, cin x cout x hin, stride, shortcut mode."""
+    cin, cout, hin, stride = INF_GEOM[l]
+    role = "stem" if l == 0 else f"s{(l - 1) // 6}b{(l - 1) % 6 // 2}{'ab'[(l - 1) % 2]}"
+    return f"l{l:02d}-{role}-{cin}x{cout}x{hin}s{stride}-sc{INF_SC[l]}"
+
+
+def _lg(t):
+    """log2 of the largest power of two that divides each fp64 element (_BIG for zero)."""
+    t = t.detach().to(F64)
+    m, e = torch.frexp(t)                                  # t = m 2^e, 0.5 <= |m| < 1
+    mi = (m.abs() * 2.0 ** 53).to(torch.int64)
+    _, e2 = torch.frexp((mi & -mi).double())               # the lowest set bit of the significand is 2^(e2 - 1)
+    return torch.where(t == 0, torch.full_like(e, _BIG, dtype=torch.int64), (e - 53 + e2 - 1).to(torch.int64))
+
+
+def _need_exact(name, lg, abs_sum):
+    """Every term a multiple of 2^lg and sum |terms| < 2^24 2^lg, element-wise; raises with ``name``."""
+    room = torch.ldexp(torch.full_like(abs_sum, float(LIM)), lg.expand_as(abs_sum).to(torch.int32))
+    bad = ~(abs_sum < room)
+    if bool(bad.any()):
+        worst = float((abs_sum / room)[bad].max())
+        raise AssertionError(f"{name}: {int(bad.sum())} of {bad.numel()} fp32 sums are not exact in every order "
+                             f"(worst sum |terms| / (2^24 granule) = {worst:.3g})")
+
+
+def _need_conv_exact(name, x, w, stride):
+    """The MFMA sums of one layer.  Granule of an output's terms: the smallest granule of the inputs in
+    its window (all channels, halo excluded) times the smallest granule of a non-zero weight -- a lower
+    bound of the true one, so the condition is sufficient."""
+    x, w = x.detach(), w.detach()
+    hout = x.shape[1] // stride
+    xp = _xpad(_lg(x).amin(3, keepdim=True).double(), stride, fill=float(_BIG))
+    lg = torch.full((x.shape[0], hout, hout, 1), float(_BIG), dtype=F64)
+    for kh in range(3):
+        for kw in range(3):
+            lg = torch.minimum(lg, _tap(xp, kh, kw, stride, hout))
+    lgw = int(_lg(w).min())
+    _need_exact(f"{name} conv", lg.long() + (lgw if lgw < _BIG else 0), conv3x3(x.abs(), w.abs(), stride))
+
+
+def infer_bn_f32(gamma, beta, mm, mv):
+    """k_rn_infer's BatchNorm fold in numpy float32, operation by operation, in its expression order
+    (one rounding per operation; an fma of the last line gives the same when the results are exact)."""
+    import numpy as np
+    g, b, m, v = (np.asarray(t.detach().cpu().numpy(), dtype=np.float32) for t in (gamma, beta, mm, mv))
+    sc = g * (np.float32(1.0) / np.sqrt(v + np.float32(BN_EPS)))
+    sh = b - m * sc
+    assert sc.dtype == np.float32 and sh.dtype == np.float32
+    return torch.from_numpy(sc).double(), torch.from_numpy(sh).double()
+
+
+def _rb(t, check):
+    """bf16 round-to-nearest-even of values fp32 holds exactly (so fp64 -> fp32 -> bf16 rounds once)."""
+    f = t.float()
+    if check:
+        assert torch.equal(f.double(), t.detach()), "a stored value is not an fp32 number"
+    return f.to(torch.bfloat16).to(F64)
+
+
+def infer_exact(images, weights, gamma, beta, mm, mv, fcw, fcb, rounded=True, check=True, f32_bn=True, round_last=False,
+                tb_shift=None, leaf=None):
+    """k_rn_infer in fp64 on the CPU: images [B, 32, 32, 3] (raw 0..255), 19 HWIO kernels, per-layer
+    gamma / beta / moving mean / moving variance, fc [64, 10] + [10].  Returns logits [B, 10], pred (the
+    FIRST maximum), ``stored`` (every layer's output as the kernel keeps it: bf16-rounded, layer 18
+    unrounded), ``pre`` (the pre-ReLU values) and ``pooled``.
+
+    ``rounded``: round to bf16 at the kernel's store points (False: the plain fp64 network).  ``check``:
+    assert the exact-accumulation preconditions of every layer, the pool and the fc.  ``f32_bn``: fold
+    BatchNorm as the kernel does, in float32 (False: fp64 from the definition).  ``leaf``: detach layer
+    ``leaf``'s stored output (18: the pooled values) into an autograd leaf, returned as ``leaf``.
+    Deliberate breaks, for the tests of the tests: ``round_last`` rounds layer 18 to bf16 before the pool;
+    ``tb_shift=l`` reads layer l's scale / shift one channel late."""
+    rb = (lambda t: _rb(t, check)) if rounded else (lambda t: t)
+    fcw, fcb = fcw.to(F64), fcb.to(F64)
+    o = types.SimpleNamespace(stored=[], pre=[], leaf=None)
+
+    def layer(l, x, src):
+        cin, cout, hin, stride = INF_GEOM[l]
+        name = infer_layer_id(l)
+        w = weights[l].to(F64)
+        assert tuple(x.shape[1:]) == (hin, hin, cin) and tuple(w.shape) == (3, 3, cin, cout), name
+        if f32_bn:
+            sc, sh = infer_bn_f32(gamma[l], beta[l], mm[l], mv[l])
+        else:
+            sc = gamma[l].to(F64) / torch.sqrt(mv[l].to(F64) + BN_EPS)
+            sh = beta[l].to(F64) - mm[l].to(F64) * sc
+        if tb_shift == l:
+            sc, sh = sc.roll(-1), sh.roll(-1)
+        acc = conv3x3(x, w, stride)
+        s = shortcut(src, INF_SC[l])
+        v = acc * sc + sh + s
+        if check:
+            _need_conv_exact(name, x, w, stride)
+            terms = [acc.detach() * sc, sh.expand_as(acc)] + ([s.detach()] if INF_SC[l] else [])
+            lg = torch.stack([_lg(t) for t in terms]).amin(0)
+            _need_exact(f"{name} scale / shift / shortcut", lg, sum(t.abs() for t in terms))
+        o.pre.append(v.detach())
+        out = v.clamp(min=0)                  # d/dv = 1 at v == 0: the derivative towards the values a store can take
+        if l < INF_LAYERS - 1 or round_last:
+            out = rb(out)
+        if leaf == l and l < INF_LAYERS - 1:
+            out = o.leaf = out.detach().requires_grad_(True)
+        o.stored.append(out)
+        return out
+
+    x = rb(images.to(F64))
+    cur = layer(0, x, None)
+    for blk in range(9):
+        y = layer(1 + 2 * blk, cur, None)
+        cur = layer(2 + 2 * blk, y, cur)
+    if check:
+        d = cur.detach()
+        _need_exact("pool", _lg(d).amin((1, 2)), d.abs().sum((1, 2)))
+    o.pooled = cur.sum((1, 2)) / 64
+    if leaf == INF_LAYERS - 1:
+        o.pooled = o.leaf = o.pooled.detach().requires_grad_(True)
+    if check:
+        terms = torch.cat([o.pooled.detach()[:, :, None] * fcw[None], fcb.expand(cur.shape[0], 1, 10)], 1)
+        _need_exact("fc", _lg(terms).amin(1), terms.abs().sum(1))
+    o.logits = o.pooled @ fcw + fcb
+    m = o.logits.detach().max(1, keepdim=True).values
+    o.tie = (o.logits.detach() == m).sum(1) > 1
+    o.pred = torch.where(o.logits.detach() == m, torch.arange(10), 10).min(1).values
+    return o
+
+
+# --------------------------------------------------------------------------------------------------
+# inference cases
+def _delta(cin, cout):
+    """centre tap, output channel co copies input channel co % cin"""
+    w, co = torch.zeros(3, 3, cin, cout), torch.arange(cout)
+    w[1, 1, co % cin, co] = 1
+    return w
+
+
+def _box(cin, cout):
+    """stride-2 carrier: taps (0..1, 0..1) of input channel co % cin -- rows 2y, 2y + 1 and columns 2x,
+    2x + 1, so every input pixel reaches exactly one output pixel"""
+    w, co = torch.zeros(3, 3, cin, cout), torch.arange(cout)
+    for kh in range(2):
+        for kw in range(2):
+            w[kh, kw, co % cin, co] = 1
+    return w
+
+
+def stem_colour(co):
+    return (co + co // 9) % 3
+
+
+def _stem_carrier():
+    """one tap per output channel: channel co is colour stem_colour(co) shifted by tap co % 9"""
+    w = torch.zeros(3, 3, 3, 16)
+    for co in range(16):
+        w[co % 9 // 3, co % 3, stem_colour(co), co] = 1
+    return w
+
+
+INFER_ROWS = 5                                   # data rows of every case: random, bright, all-zero, random, random
+INFER_PMAX = (7,) + (3,) * 6 + (15, 15) + (7,) * 4 + (15,) * 6      # pixel range of the ``layer`` cases (see make_infer_case)
+TIE_FAV = {0: (2, 5), 1: (7,), 2: (4, 9)}        # the classes the channels of each stem colour favour
+INFER_CASES = tuple(("layer", l, 100 + l) for l in range(INF_LAYERS)) + (("range", None, 31), ("pool", None, 32),
+                                                                         ("tie", None, 33))
+INFER_GEOM_LAYERS = (0, 3, 7, 10, 13, 16)       # one layer per geometry: stem, 16/16, 16->32, 32/32, 32->64, 64/64
+
+
+def infer_case_id(case):
+    return infer_layer_id(case[1]) if case[0] == "layer" else case[0]
+
+
+@functools.lru_cache(maxsize=None)
+def make_infer_case(kind, layer, seed):
+    """Seeded inputs of one k_rn_infer launch and the oracle's results on all INFER_ROWS data rows
+    (cached: treat as read-only).
+
+    ``layer`` l: layer l has dense integer weights in -2..2 and a per-channel BatchNorm (sc = gamma 2^-k
+    with k in {-1, 0, 1} and gamma in {-2, -1, 1, 2}; non-zero integer beta and moving mean); every other
+    layer is a non-negative carrier with sc = 1 (or 0), sh = 0:
+      * the stem copies one (tap, colour) per output channel;
+      * every a-conv of a stride-1 block is the centre-tap identity; its b-conv has gamma = 0 (the block is
+        the identity through its shortcut) unless the block holds layer l, then it is the identity too;
+      * a stride-2 block UPSTREAM of l is identity a-conv + identity b-conv (+ option A): no growth;
+        DOWNSTREAM of l its a-conv sums the 2x2 pixels (2y..2y+1, 2x..2x+1) of its channel, so every pixel
+        of layer l's output reaches the pool, and output channels co and co + cin both copy channel co;
+      * the fc weights are integers 1..2, all ten columns different.
+    The downstream carrier is 2x2, not 3x3: the head sums 64 pixels x 64 channels x an fc weight, 14 bits
+    of the 24, so the LAST layer's values may average about 2^10 granules; a 3x3 sum grows them ~10x per
+    stage and would leave the layer under test almost none.  For the same reason the early layers' cases
+    use smaller pixels (INFER_PMAX).  The oracle's assertions decide: every case must pass them.
+
+    ``range``: carriers only (all stride-2 a-convs identity), pixels over the whole 0..255.
+    ``pool``: as ``range``, but layer 18 is identity + shortcut + 1: odd values up to 2041 enter the pool.
+    ``tie``: carriers only; single-colour images and fc columns by colour so that classes tie."""
+    r = _Rng(seed)
+    L = INF_LAYERS
+    c = types.SimpleNamespace(kind=kind, layer=layer, seed=seed, id=infer_case_id((kind, layer, seed)))
+    lut = layer if kind == "layer" else L                 # stride-2 a-convs below ``lut`` do not grow
+    c.w, c.gamma, c.beta, c.mm, c.kexp = [], [], [], [], []
+    for l in range(L):
+        cin, cout, hin, stride = INF_GEOM[l]
+        is_b = l > 0 and l % 2 == 0
+        blk_has_l = kind == "layer" and l > 0 and (l - 1) // 2 == (layer - 1) // 2 and layer > 0
+        if kind == "layer" and l == layer:
+            w = r.ints(-2, 2, 3, 3, cin, cout).float()
+            k = r.pick([-1, 0, 1], cout)
+            k[:3] = torch.tensor([-1, 0, 1])
+            g = r.pick([-2, -1, 1, 2], cout).float()
+            g[3], g[4] = -1, 2
+            b, m = r.pick([-3, -2, -1, 1, 2, 3], cout).float(), r.pick([-3, -2, -1, 1, 2, 3], cout).float()
+        else:
+            w = _stem_carrier() if l == 0 else (_box(cin, cout) if stride == 2 and l > lut else _delta(cin, cout))
+            passes = not is_b or stride == 2 or INF_SC[l] == 2 or blk_has_l
+            if kind == "pool" and l == L - 1:
+                passes = True
+            k = torch.zeros(cout, dtype=torch.int64)
+            g = torch.full((cout,), 1.0 if passes else 0.0)
+            b, m = torch.zeros(cout), torch.zeros(cout)
+            if kind == "pool" and l == L - 1:
+                b = torch.ones(cout)
+        c.w.append(w), c.gamma.append(g), c.beta.append(b), c.mm.append(m), c.kexp.append(k)
+    c.mv = [(4.0 ** k.double() - BN_EPS).float() for k in c.kexp]
+    c.sc = [g.double() * 2.0 ** -k.double() for g, k in zip(c.gamma, c.kexp)]             # the intended fold
+    c.sh = [b.double() - m.double() * s for b, m, s in zip(c.beta, c.mm, c.sc)]
+
+    pmax = INFER_PMAX[layer] if kind == "layer" else (255 if kind in ("range", "pool") else 15)
+    img = r.ints(0, pmax, INFER_ROWS, 32, 32, 3)
+    img[1] = r.ints(pmax - pmax // 4, pmax, 32, 32, 3)      # a bright image, then an all-zero one
+    img[2] = 0
+    if kind in ("range", "pool"):
+        img[0, 0, :4, 0] = torch.tensor([0, 127, 128, 255])
+        img[1, 5, 5] = 255
+    if kind == "tie":                                        # rows 0, 4 red only, 1 green only, 2 blue only, 3 mixed
+        img[2] = r.ints(0, pmax, 32, 32, 3)
+        img[3] = r.ints(0, 7, 32, 32, 3)
+        img[3, :, :, 1] += 8                                 # mostly green: class 7 alone
+        for row, colour in ((0, 0), (1, 1), (2, 2), (4, 0)):
+            keep = torch.zeros(3, dtype=torch.int64)
+            keep[colour] = 1
+            img[row] *= keep
+    c.images = img.to(torch.uint8)
+
+    if kind == "tie":
+        fav = torch.zeros(64, 10)
+        for ch in range(64):
+            fav[ch, list(TIE_FAV[stem_colour(ch % 16)])] = 1
+        c.fcw = 1 + 2 * fav
+        c.fcb = torch.tensor([3., -2, 1, 0, -1, 1, 2, -3, 4, -1])           # equal within (2, 5) and (4, 9)
+    else:
+        c.fcw = r.ints(1, 2, 64, 10).float()
+        c.fcb = (torch.randperm(10, generator=r.g) - 4).float()
+        assert c.fcw.t().unique(dim=0).shape[0] == 10, "two fc columns are equal"
+
+    o = c.o = infer_exact(img, c.w, c.gamma, c.beta, c.mm, c.mv, c.fcw, c.fcb)
+    assert bool(torch.isfinite(o.logits).all()) and torch.equal(o.logits.float().double(), o.logits)
+    # labels (one per data row): the first tied image gets the LATER of its tied classes, so a
+    # last-maximum rule would call it correct; otherwise hits and misses alternate
+    lab = torch.where(torch.arange(INFER_ROWS) % 2 == 0, o.pred, (o.pred + 1) % 10)
+    for b in o.tie.nonzero().flatten().tolist()[:1]:
+        lab[b] = int((o.logits[b] == o.logits[b].max()).nonzero().max())
+    c.labels = lab.to(torch.int32)
+
+    if kind == "layer":
+        pre = o.pre[layer]
+        c.negative = float((pre < 0).double().mean())
+        assert 0.2 <= c.negative <= 0.8, f"{c.id}: {c.negative:.0%} of the pre-ReLU values are negative"
+        assert set(c.kexp[layer].tolist()) == {-1, 0, 1} and bool((c.gamma[layer] < 0).any())
+        for name, edge in (("top", pre[:, 0]), ("bottom", pre[:, -1]), ("left", pre[:, :, 0]), ("right", pre[:, :, -1])):
+            assert float((edge > 0).double().mean()) >= 0.1, f"{c.id}: the {name} border is nearly dead"
+        x_in = img.double() if layer == 0 else o.stored[layer - 1]
+        assert bool((x_in[0].sum((0, 1)) > 0).all()), f"{c.id}: an input channel of the layer under test is empty"
+        assert bool(x_in[0, 0].any()) and bool(x_in[0, -1].any()) and bool(x_in[0, :, 0].any()) and bool(x_in[0, :, -1].any())
+    if kind in ("range", "pool"):
+        assert {0, 127, 128, 255} <= set(c.images.unique().tolist())
+    if kind == "pool":
+        last = o.stored[L - 1]
+        assert bool((_rb(last, True) != last).any()), "every pre-pool value fits bf16"
+    if kind == "tie":
+        assert bool(o.tie[0]) and int(o.pred[0]) == 2 and int(c.labels[0]) == 5
+        assert int(o.pred[1]) == 7 and not bool(o.tie[1]) and bool(o.tie[2]) and int(o.pred[2]) == 4
+        assert not bool(o.tie[3]) and bool((o.pred != 0).all())
+    return c
+
+
+def infer_buffers(c, seed=0):
+    """``master`` and ``state`` as rn_infer reads them, with the op's offset arguments: the 19 gamma and
+    beta tables and the fc (master), the 19 moving means and variances (state) in a shuffled order with
+    gaps of 1..40 words between them -- not the order of models/resnet.py PARAM_SPECS -- and every other
+    word NaN, so a read at a wrong offset or past a table's channels poisons a logit."""
+    r = _Rng(1000 + seed)
+
+    def lay(items):
+        off, pos = {}, int(r.ints(1, 40, 1))
+        for i in torch.randperm(len(items), generator=r.g).tolist():
+            off[items[i][0]] = pos
+            pos += items[i][1].numel() + int(r.ints(1, 40, 1))
+        buf = torch.full((pos,), float("nan"), dtype=torch.float32)
+        for key, t in items:
+            buf[off[key]:off[key] + t.numel()] = t.reshape(-1).float()
+        return buf, off
+
+    L = range(INF_LAYERS)
+    master, po = lay([(("gamma", l), c.gamma[l]) for l in L] + [(("beta", l), c.beta[l]) for l in L]
+                     + [("fcw", c.fcw), ("fcb", c.fcb)])
+    state, so = lay([(("mm", l), c.mm[l]) for l in L] + [(("mv", l), c.mv[l]) for l in L])
+    return types.SimpleNamespace(master=master, state=state, gamma_off=[po["gamma", l] for l in L],
+                                 beta_off=[po["beta", l] for l in L], mm_off=[so["mm", l] for l in L],
+                                 mv_off=[so["mv", l] for l in L], fcw_off=po["fcw"], fcb_off=po["fcb"])

@@ -260,3 +260,140 @@ def test_gpu_pair_tables_equal_the_engines_layers():
     ran = {(c[0], c[1], c[5]) for c in X.GPU_CASES if c[4] == 16}
     assert {("fwd", g, m) for g, m in X.FWD_PAIRS} <= ran and {("bwd", g, m) for g, m in X.BWD_PAIRS} <= ran
     assert all(((g, X.BWD_DEFAULT_MODE[g]) in X.BWD_PAIRS) for g in X.GEOMS[1:])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the whole-network inference oracle (X.infer_exact) and the cases of tests/test_rn_infer_exact_gpu.py
+INFER_IDS = [X.infer_case_id(c) for c in X.INFER_CASES]
+LAYER_CASES = [c for c in X.INFER_CASES if c[0] == "layer"]
+
+
+def _case_args(c):
+    return c.images, c.w, c.gamma, c.beta, c.mm, c.mv, c.fcw, c.fcb
+
+
+def test_infer_oracle_without_roundings_is_the_models_eval_forward():
+    """infer_exact with no bf16 rounding and the fp64 BatchNorm fold equals models/resnet.py's eval-mode
+    forward in fp64 on random real parameters and moving statistics (every layer's geometry, stride,
+    shortcut mode and channel order; the pool; the fc)."""
+    g = torch.Generator().manual_seed(5)
+    flat, state = R.init_flat_params(g)
+    flat, state = flat.double(), state.double()
+    for s in R.PARAM_SPECS:
+        if not s.name.endswith("kernel") and not s.name.endswith("weights"):
+            flat[s.offset:s.offset + s.numel] = torch.randn(s.numel, generator=g, dtype=F64)
+    for s in R.STATE_SPECS:
+        v = torch.rand(s.numel, generator=g, dtype=F64) + 0.5 if s.name.endswith("variance") else torch.randn(s.numel, generator=g, dtype=F64)
+        state[s.offset:s.offset + s.numel] = v
+    p, st = R._views(flat, R.PARAM_SPECS), R._views(state, R.STATE_SPECS)
+    names = [L[0] for L in E.LAYERS]
+    assert len(names) == X.INF_LAYERS and [tuple(L[1:5]) for L in E.LAYERS] == list(X.INF_GEOM)
+    images = torch.randint(0, 256, (3, 32, 32, 3), generator=g)
+    o = X.infer_exact(images, [p[f"{n}/conv/kernel"] for n in names], [p[f"{n}/bn/gamma"] for n in names],
+                      [p[f"{n}/bn/beta"] for n in names], [st[f"{n}/bn/moving_mean"] for n in names],
+                      [st[f"{n}/bn/moving_variance"] for n in names], p["fc/weights"], p["fc/biases"], rounded=False,
+                      check=False, f32_bn=False)
+    want = R.resnet20_forward(images.double(), p, st, training=False)
+    assert float(want.abs().max()) > 0.1 and torch.allclose(o.logits, want, rtol=1e-11, atol=1e-9)
+    assert torch.equal(o.pred, want.argmax(1))
+
+
+def test_infer_shortcut_modes_equal_the_plans():
+    from dmlc.engine.plan_resnet import plan_resnet_step
+    plan = plan_resnet_step(batch_size=16)
+    # the forward launch of layer l + 1 applies layer l's epilogue: its shortcut mode is layer l's
+    assert [plan.fwd_sc[l + 1][0] for l in range(X.INF_LAYERS - 1)] == list(X.INF_SC[:-1]) and X.INF_SC[-1] == 1
+
+
+def test_infer_precondition_names_the_layer():
+    c = X.make_infer_case("layer", 10, 110)
+    w = [t.clone() for t in c.w]
+    w[10] = w[10] * 65537                              # 17 more bits in every term of layer 10
+    with pytest.raises(AssertionError, match="l10-s1b1b-32x32x16s1-sc1"):
+        X.infer_exact(c.images, w, c.gamma, c.beta, c.mm, c.mv, c.fcw, c.fcb)
+    assert X._lg(torch.tensor([0., 1., 6., 0.75, 1024., -3.5], dtype=F64)).tolist() == [X._BIG, 0, 1, -2, 10, -1]
+
+
+@pytest.mark.parametrize("case", X.INFER_CASES, ids=INFER_IDS)
+def test_infer_cases_meet_their_preconditions(case):
+    """make_infer_case runs the oracle with every accumulation precondition asserted and checks what its
+    kind needs (share of negative pre-ReLU values, pixel values, ties).  Here, in addition: the kernel's
+    BatchNorm fold, emulated in numpy float32 in its expression order, gives exactly the intended
+    sc = gamma 2^-k and sh = beta - mm sc; the buffers hold NaN outside the tables and are not in
+    PARAM_SPECS order; the labels give hits and misses."""
+    import numpy as np
+    c = X.make_infer_case(*case)
+    for l in range(X.INF_LAYERS):
+        assert bool(np.all(c.mv[l].numpy() + np.float32(X.BN_EPS) == np.float32(4.0) ** c.kexp[l].numpy().astype(np.float32)))
+        sc, sh = X.infer_bn_f32(c.gamma[l], c.beta[l], c.mm[l], c.mv[l])
+        assert torch.equal(sc, c.sc[l]) and torch.equal(sh, c.sh[l]), X.infer_layer_id(l)
+    if case[0] == "layer":
+        l = case[1]
+        print(f"{c.id}: {c.negative:.1%} of the pre-ReLU values are negative")
+        assert bool((c.sh[l] != c.sh[l].round()).any()) and c.sc[l].unique().numel() >= 4
+        assert bool((c.w[l] == 0).double().mean() < 0.3)
+    b = X.infer_buffers(c, case[2])
+    used_p = 2 * sum(g[1] for g in X.INF_GEOM) + 650
+    assert int(torch.isfinite(b.master).sum()) == used_p < b.master.numel()
+    assert int(torch.isfinite(b.state).sum()) == used_p - 650 < b.state.numel()
+    assert b.gamma_off != sorted(b.gamma_off) and b.mv_off != sorted(b.mv_off)
+    for l in range(X.INF_LAYERS):
+        co = X.INF_GEOM[l][1]
+        assert torch.equal(b.master[b.gamma_off[l]:b.gamma_off[l] + co], c.gamma[l])
+        assert torch.equal(b.state[b.mv_off[l]:b.mv_off[l] + co], c.mv[l])
+        for off, buf in ((b.gamma_off[l], b.master), (b.beta_off[l], b.master), (b.mm_off[l], b.state), (b.mv_off[l], b.state)):
+            assert bool(torch.isnan(buf[off - 1])) and bool(torch.isnan(buf[off + co]))
+    assert torch.equal(b.master[b.fcw_off:b.fcw_off + 640].view(64, 10), c.fcw)
+    hits = (c.o.pred == c.labels.long())
+    assert bool(hits.any()) and not bool(hits.all())
+    assert not bool(c.images[2].any()) or case[0] == "tie"
+    assert float(c.images[1].double().mean()) > float(c.images[0].double().mean()) or case[0] == "tie"
+
+
+@pytest.mark.parametrize("case", LAYER_CASES, ids=[X.infer_case_id(c) for c in LAYER_CASES])
+def test_infer_layer_cases_hide_no_element(case):
+    """Sensitivity: in the oracle without roundings (fp64 autograd), EVERY element of the stored output
+    of the layer under test (layer 18: every pooled value) has a non-zero gradient to at least one
+    compared logit, so no wrong pixel or channel of that layer can stay invisible.  ReLU is clamp(min=0),
+    whose derivative is 1 at 0: a stored value is >= 0, so the derivative towards larger values is the
+    one that says whether a wrong stored zero would show."""
+    c = X.make_infer_case(*case)
+    l = case[1]
+    o = X.infer_exact(*_case_args(c), rounded=False, check=False, leaf=l)
+    want_shape = (X.INFER_ROWS, 64) if l == 18 else (X.INFER_ROWS, X.INF_GEOM[l][2] // X.INF_GEOM[l][3],
+                                                     X.INF_GEOM[l][2] // X.INF_GEOM[l][3], X.INF_GEOM[l][1])
+    assert tuple(o.leaf.shape) == want_shape
+    seen = torch.zeros(want_shape, dtype=torch.bool)
+    for n in range(10):                               # images are independent: one backward per class
+        (grad,) = torch.autograd.grad(o.logits[:, n].sum(), o.leaf, retain_graph=True)
+        seen |= grad != 0
+    assert bool(seen.all()), f"{c.id}: {int((~seen).sum())} of {seen.numel()} elements reach no logit"
+
+
+@pytest.mark.parametrize("case", LAYER_CASES, ids=[X.infer_case_id(c) for c in LAYER_CASES])
+def test_infer_broken_oracle_differs(case):
+    """The tests of the tests: an oracle that reads the layer under test's scale / shift one channel late
+    gives other logits for that layer's case, in every image."""
+    c = X.make_infer_case(*case)
+    bad = X.infer_exact(*_case_args(c), check=False, tb_shift=case[1])
+    differs = (bad.logits != c.o.logits).any(1)
+    assert bool(differs.all()), differs
+
+
+@pytest.mark.parametrize("kind,layer,seed", [c for c in X.INFER_CASES if c[0] == "pool" or c[1] == 18])
+def test_infer_rounding_the_last_layer_differs(kind, layer, seed):
+    """An oracle that rounds layer 18 to bf16 before the pool, as every other layer is rounded, gives
+    other logits: the ``pool`` case (and the case of layer 18) would catch a kernel that did."""
+    c = X.make_infer_case(kind, layer, seed)
+    bad = X.infer_exact(*_case_args(c), check=False, round_last=True)
+    differs = (bad.logits != c.o.logits).any(1)
+    assert bool(differs[[0, 1, 3, 4]].all()), differs
+    assert bool((bad.stored[18] != c.o.stored[18]).any())
+
+
+def test_infer_tie_case_ties():
+    c = X.make_infer_case(*[k for k in X.INFER_CASES if k[0] == "tie"][0])
+    o = c.o
+    assert o.tie.tolist() == [True, False, True, False, True] and o.pred.tolist() == [2, 7, 4, 7, 2]
+    last_max = torch.stack([(o.logits[b] == o.logits[b].max()).nonzero().max() for b in range(X.INFER_ROWS)])
+    assert last_max.tolist() == [5, 7, 9, 7, 5] and int(c.labels[0]) == 5       # a last-maximum rule: image 0 "correct"
