@@ -793,6 +793,81 @@ void backward_fused(const Tensor& master, const Buf& buf, const Tensor& idx, con
   CHECK_HIP(dmlc_backward(&a, &g, &w, hand, stream_of(master)));
 }
 
+// The whole eval-mode forward in one launch (cnn_infer.hip): image i is data[idx[i]] (idx None: data[i],
+// N = data rows); writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels, one per
+// data row).  Reads the bf16 shadows, slot step & 1 of fc1n and the five bias views of master at `off`;
+// scratch: bf16 [S, 16, 2304] with S >= the launch's workgroups, min(ceil(N / 16), blocks or the CUs).
+void cnn_infer(const Tensor& data, const c10::optional<Tensor>& idx, const c10::optional<Tensor>& labels, int64_t cy,
+               int64_t cx, const Tensor& w1f, const Tensor& w2f, const Tensor& fc1n, const Tensor& step,
+               const Tensor& fc2t, const Tensor& fc3t, const Tensor& master, at::IntArrayRef off, bool relu_logits,
+               const Tensor& scratch, const Tensor& logits, const c10::optional<Tensor>& pred,
+               const c10::optional<Tensor>& correct, int64_t blocks) {
+  check_data(data);
+  const int64_t rows = data.size(0), N = idx.has_value() ? idx->numel() : rows;
+  TORCH_CHECK(rows >= 1 && rows < (1ll << 31) / 3072 * 16, "cnn_infer: data rows out of range");
+  TORCH_CHECK(N >= 1 && N < (1ll << 31) / 10, "cnn_infer: 1 <= N < 2^31 / 10");
+  TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "cnn_infer: blocks must be >= 0 (0: one workgroup per CU)");
+  TORCH_CHECK(cy >= 0 && cy <= 8 && cx >= 0 && cx <= 8, "crop offsets must be in [0,8]");
+  const auto same_dev = [&](const Tensor& t, const char* n) {
+    TORCH_CHECK(t.device() == data.device(), "cnn_infer: ", n, " must be on data's device");
+  };
+  DmlcCnnInferArgs a;
+  memset(&a, 0, sizeof(a));
+  a.data = data.data_ptr<uint8_t>(); a.nrows = (int)rows;
+  a.N = (int)N; a.cy = (int)cy; a.cx = (int)cx; a.blocks = (int)blocks; a.relu_logits = relu_logits ? 1 : 0;
+  if (idx.has_value()) {
+    check_numel(*idx, "idx", at::kInt, N);
+    same_dev(*idx, "idx");
+    a.idx = idx->data_ptr<int>();
+  }
+  if (labels.has_value()) {
+    check_numel(*labels, "labels", at::kInt, rows);
+    same_dev(*labels, "labels");
+    a.labels = labels->data_ptr<int>();
+  }
+  check(w1f, "w1f", at::kBFloat16, {64, 96});
+  check(w2f, "w2f", at::kBFloat16, {64, 1600});
+  check(fc1n, "fc1n", at::kBFloat16, {2, 2304, 384});
+  check_numel(step, "step", at::kLong, 1);
+  check(fc2t, "fc2t", at::kBFloat16, {192, 384});
+  check(fc3t, "fc3t", at::kBFloat16, {16, 192});
+  same_dev(w1f, "w1f"); same_dev(w2f, "w2f"); same_dev(fc1n, "fc1n"); same_dev(step, "step");
+  same_dev(fc2t, "fc2t"); same_dev(fc3t, "fc3t");
+  a.w1f = w1f.data_ptr(); a.w2f = w2f.data_ptr(); a.fc1n = fc1n.data_ptr(); a.step = step.data_ptr<int64_t>();
+  a.fc2t = fc2t.data_ptr(); a.fc3t = fc3t.data_ptr();
+  // the biases: views of the flat fp32 master (fc1's and fc2's are read as 16-B vectors)
+  check_min(master, "master", at::kFloat, check_off(off));
+  same_dev(master, "master");
+  const float* m = master.data_ptr<float>();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(m) % 16 == 0 && off[5] % 4 == 0 && off[7] % 4 == 0,
+              "cnn_infer: the fc1 / fc2 bias views must be 16-byte aligned");
+  a.b1 = m + off[1]; a.b2 = m + off[3]; a.fb1 = m + off[5]; a.fb2 = m + off[7]; a.fb3 = m + off[9];
+  c10::DeviceGuard guard(data.device());
+  int grid = 0;
+  CHECK_HIP(dmlc_cnn_infer_grid((int)N, (int)blocks, &grid));
+  dev(scratch, "scratch");
+  same_dev(scratch, "scratch");
+  TORCH_CHECK(scratch.scalar_type() == at::kBFloat16 && scratch.dim() == 3 && scratch.size(1) == 16 &&
+                  scratch.size(2) == 2304 && scratch.size(0) >= grid,
+              "cnn_infer: scratch must be bf16 [S >= ", grid, " workgroups, 16, 2304], got ", scratch.sizes());
+  a.scratch = scratch.data_ptr(); a.scratch_slabs = (int)std::min<int64_t>(scratch.size(0), 1 << 30);
+  check(logits, "logits", at::kFloat, {N, 10});
+  same_dev(logits, "logits");
+  a.logits = logits.data_ptr<float>();
+  if (pred.has_value()) {
+    check_numel(*pred, "pred", at::kInt, N);
+    same_dev(*pred, "pred");
+    a.pred = pred->data_ptr<int>();
+  }
+  if (correct.has_value()) {
+    TORCH_CHECK(labels.has_value(), "cnn_infer: correct needs labels");
+    check_numel(*correct, "correct", at::kInt, N);
+    same_dev(*correct, "correct");
+    a.correct = correct->data_ptr<int>();
+  }
+  CHECK_HIP(dmlc_cnn_infer(&a, stream_of(data)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmlc, m) {
@@ -822,6 +897,9 @@ TORCH_LIBRARY(dmlc, m) {
         "Tensor labels, Tensor idx, Tensor? counter, int period, float inv_batch, bool relu_logits, bool train, "
         "Tensor(a!) h1, Tensor(b!) h2, Tensor(c!) dl, Tensor(d!) dh1, Tensor(e!) dh2, Tensor(f!) loss_part, "
         "Tensor(g!) correct_part, Tensor(h!)? logits_out, int nvalid=-1, Tensor? step=None, Tensor(i!)? step_copy=None) -> ()");
+  m.def("cnn_infer(Tensor data, Tensor? idx, Tensor? labels, int cy, int cx, Tensor w1f, Tensor w2f, Tensor fc1n, "
+        "Tensor step, Tensor fc2t, Tensor fc3t, Tensor master, int[] off, bool relu_logits, Tensor(a!) scratch, "
+        "Tensor(b!) logits, Tensor(c!)? pred, Tensor(d!)? correct, int blocks=0) -> ()");
   // the engine-level ops: master, the named buffers, then what differs from call to call
   m.def("fc_chain(Tensor(a!) master, Dict(str, Tensor) buf, Tensor idx, Tensor? counter, int period, int[] off, "
         "float[] sched, int batch, float inv_batch, bool relu_logits, bool fuse_sgd, bool dw_tasks, bool dgrad, "
@@ -851,6 +929,7 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("wgrad", &wgrad);
   m.impl("gemm_grouped", &gemm_grouped);
   m.impl("head", &head);
+  m.impl("cnn_infer", &cnn_infer);
   m.impl("fc_chain", &fc_chain);
   m.impl("sgd", &sgd);
   m.impl("xgmi_allreduce_sgd", &xgmi_allreduce_sgd);

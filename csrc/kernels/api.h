@@ -322,6 +322,30 @@ struct DmlcWgradArgs {
   int fc_done;              // apply mode: the fc chain already applied every fc SGD (fuse_sgd 2): no fc roles
 };
 
+// Eval-mode forward of the whole CNN in ONE launch (cnn_infer.hip): N images from uint8 pixels to
+// logits.  Persistent workgroups, each taking tiles of 16 images from pixels to logits on its own; image
+// i is data[idx ? idx[i] : i] (clamped to [0, nrows)) at the crop (cy, cx).  Reads the bf16 shadows and
+// the fp32 biases as the last step left them, writes nothing but its outputs and its scratch.
+struct DmlcCnnInferArgs {
+  const uint8_t* data; int nrows;    // [nrows][32][32][3] uint8
+  const int* idx;                    // nullable [N]
+  const int* labels;                 // nullable [nrows] (needed for `correct`)
+  int N, cy, cx;
+  const void* w1f; const float* b1;  // bf16 [64][96], [64]
+  const void* w2f; const float* b2;  // bf16 [64][1600], [64]
+  const void* fc1n;                  // bf16 [2][2304][384]: slot *step & 1 is read
+  const int64_t* step;               // device step counter
+  const float* fb1;                  // [384]
+  const void* fc2t; const float* fb2;   // bf16 [192][384], [192]
+  const void* fc3t; const float* fb3;   // bf16 [16][192] (rows >= 10 zero), [10]
+  int relu_logits;
+  void* scratch; int scratch_slabs;  // bf16 [scratch_slabs][16][2304]: one pooled-activation slab per workgroup
+  float* logits;                     // [N][10]
+  int* pred;                         // nullable [N]: first maximum
+  int* correct;                      // nullable [N]: pred == labels[row]
+  int blocks;                        // workgroups; 0 = one per CU (never more than the ceil(N / 16) tiles)
+};
+
 hipError_t dmlc_conv1_fwd(const DmlcConv1FwdArgs* a, hipStream_t s);
 hipError_t dmlc_conv2_fwd(const DmlcConv2FwdArgs* a, hipStream_t s);
 // conv1 + pool1 + conv2 + pool2 of one image per workgroup in one launch (bf16; a1->amax must be null)
@@ -358,6 +382,10 @@ hipError_t dmlc_wgrad_check(const DmlcWgradArgs* a);
 hipError_t dmlc_backward(const DmlcFcArgs* a, const DmlcConv2DgradArgs* dg, const DmlcWgradArgs* w,
                          unsigned int* hand, hipStream_t s);
 hipError_t dmlc_head(const DmlcHeadArgs* a, hipStream_t s);
+// *grid = the workgroups dmlc_cnn_infer launches for (N, blocks): min(ceil(N / 16), blocks ? blocks : CUs);
+// a->scratch_slabs must reach it
+hipError_t dmlc_cnn_infer_grid(int N, int blocks, int* grid);
+hipError_t dmlc_cnn_infer(const DmlcCnnInferArgs* a, hipStream_t s);
 hipError_t dmlc_sgd(DmlcSgdArgs* a, hipStream_t s);
 
 }  // extern "C"

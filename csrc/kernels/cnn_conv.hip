@@ -26,39 +26,6 @@
 namespace dmlc {
 
 
-// conv1 implicit GEMM of one wave: co tiles 2cp, 2cp+1 (weights wa in registers) x pixel tiles
-// 9pq .. 9pq+8.  Software-pipelined: the 3 B fragments of pixel tile t+1 are read from LDS while tile
-// t's 6 MFMAs run (wait_lds retires tile t's reads first; see common.h).
-// the wave's weight fragments: rows co0 + li (+16 for h = 1) of the [64][96] shadow
-DEV void conv1_wfrags(const void* w, int co0, int g, int li, bf16x8 (&wa)[2][3]) {
-  const bf16* W = reinterpret_cast<const bf16*>(w) + (co0 + li) * C1_K + 8 * g;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) wa[h][s] = glb_b128(W + h * 16 * C1_K + 32 * s);
-}
-DEV void conv1_mfma(const bf16* xin, const bf16x8 (&wa)[2][3], f32x4 (&acc)[2][9], int pq, int g, int li) {
-  auto load_tile = [&](int t, bf16x8 (&bx)[3]) { conv1_frag_tile(xin, (pq * 9 + t) * 16 + li, g, bx); };
-#pragma unroll
-  for (int t = 0; t < 9; ++t) { acc[0][t] = zero4(); acc[1][t] = zero4(); }
-  bf16x8 BX[2][3];
-  load_tile(0, BX[0]);
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int cur = t & 1;
-    wait_lds();
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + 1 < 9) load_tile(t + 1, BX[cur ^ 1]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      acc[0][t] = mfma16(wa[0][s], BX[cur][s], acc[0][t]);
-      acc[1][t] = mfma16(wa[1][s], BX[cur][s], acc[1][t]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT, 1) void k_conv1_fwd(DmlcConv1FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -170,10 +137,6 @@ __global__ __launch_bounds__(NT, 1) void k_conv2_dgrad(DmlcConv2DgradArgs a) {
 // Kernel row 0 of the conv2 weights is loaded into registers at entry and stored into the first
 // slice buffer after pool1: its L2 latency hides behind conv1 instead of opening the conv2 core
 // (~1 us of the core's first row, r3 phase stamps).
-constexpr size_t C12_WS = 0, C12_XIN2 = 81920, C12_OUT2 = C12_XIN2 + C2_XIN * 2;
-constexpr size_t C12_XIN1 = C12_OUT2 + C2_OUT * 2, C12_LDS = C12_XIN1 + C1_XIN * 2;
-static_assert(C1_OUT * 2 <= C12_XIN2 && WS_BYTES <= C12_XIN2 && C12_LDS <= 160 * 1024, "conv12 LDS map");
-
 __global__ __launch_bounds__(NT, 1) void k_conv12_fwd(DmlcConv1FwdArgs a1, DmlcConv2FwdArgs a2) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* xin = reinterpret_cast<bf16*>(smem + C12_XIN1);

@@ -58,6 +58,13 @@ DEV void ws_put(bf16* buf, int w, int lane, Slice5 v) {
   p[0] = v.a; p[64] = v.b; p[128] = v.c; p[192] = v.d; p[256] = v.e;
 }
 
+// LDS map of conv1 -> pool1 -> conv2 -> pool2 of one image in one workgroup (cnn_conv.hip k_conv12_fwd,
+// cnn_infer.hip): [0, 80 KB) conv1 output (72 KB), then conv2's two weight-slice buffers; [80, 112 KB)
+// conv2's padded input; [112, 130 KB) conv2's output; [130, 151 KB) conv1's input.
+constexpr size_t C12_WS = 0, C12_XIN2 = 81920, C12_OUT2 = C12_XIN2 + C2_XIN * 2;
+constexpr size_t C12_XIN1 = C12_OUT2 + C2_OUT * 2, C12_LDS = C12_XIN1 + C1_XIN * 2;
+static_assert(C1_OUT * 2 <= C12_XIN2 && WS_BYTES <= C12_XIN2 && C12_LDS <= 160 * 1024, "conv12 LDS map");
+
 // Tile ownership (r5): wave w = (cp, pg), cp = w & 1, pg = w >> 1, owns c_out tiles 2cp, 2cp+1 of the
 // pixel tiles pg and pg+4 (4 tile-units of 50 k-chunks each), and waves 0-3 also pixel tile 8 for
 // ONE c_out tile, 2cp + pg (EXTRA: 5 units).  Waves w and w+4 share a SIMD, so every SIMD carries 9

@@ -181,6 +181,39 @@ DEV void conv1_frag_tile(const bf16* xin, int px, int g, bf16x8 (&bx)[3]) {
   for (int s = 0; s < 3; ++s) bx[s] = lds_b128(base + min(2 * s + (g >> 1), 4) * 24 * 16);
 }
 
+// conv1 implicit GEMM of one wave: co tiles 2cp, 2cp+1 (weights wa in registers) x pixel tiles
+// 9pq .. 9pq+8.  Software-pipelined: the 3 B fragments of pixel tile t+1 are read from LDS while tile
+// t's 6 MFMAs run (wait_lds retires tile t's reads first; see common.h).
+// the wave's weight fragments: rows co0 + li (+16 for h = 1) of the [64][96] shadow
+DEV void conv1_wfrags(const void* w, int co0, int g, int li, bf16x8 (&wa)[2][3]) {
+  const bf16* W = reinterpret_cast<const bf16*>(w) + (co0 + li) * C1_K + 8 * g;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int s = 0; s < 3; ++s) wa[h][s] = glb_b128(W + h * 16 * C1_K + 32 * s);
+}
+DEV void conv1_mfma(const bf16* xin, const bf16x8 (&wa)[2][3], f32x4 (&acc)[2][9], int pq, int g, int li) {
+  auto load_tile = [&](int t, bf16x8 (&bx)[3]) { conv1_frag_tile(xin, (pq * 9 + t) * 16 + li, g, bx); };
+#pragma unroll
+  for (int t = 0; t < 9; ++t) { acc[0][t] = zero4(); acc[1][t] = zero4(); }
+  bf16x8 BX[2][3];
+  load_tile(0, BX[0]);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int cur = t & 1;
+    wait_lds();
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 1 < 9) load_tile(t + 1, BX[cur ^ 1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      acc[0][t] = mfma16(wa[0][s], BX[cur][s], acc[0][t]);
+      acc[1][t] = mfma16(wa[1][s], BX[cur][s], acc[1][t]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // conv2 input / output LDS images: padded [16*16][64] (swzpad) and [144][64] bf16
 constexpr int C2_XIN = 256 * 64;
 constexpr int C2_OUT = 144 * 64;
@@ -300,7 +333,9 @@ DEV void pool_window(const uint4 (&v)[9], uint4& o, uint32_t& alo, uint32_t& ahi
 // The window max / argmax: pool_window.
 // pad_lds (optional): also writes the pooled image into an LDS [(HO+4) x (HO+4)][64] swizzled image
 // at offset (2, 2) -- the zero-padded input of the next 5x5 conv (fused conv1 -> conv2 forward).
-template <int H>
+// ST_OUT / ST_AM = false: no global store of the pooled image / of the argmax bytes (inference keeps
+// neither the backward's argmax nor, for pool1, the pooled image; cnn_infer.hip).
+template <int H, bool ST_OUT = true, bool ST_AM = true>
 DEV void pool_emit(const bf16* cout, bf16* out, uint8_t* am, int tid, uint32_t* vmax = nullptr,
                    bf16* pad_lds = nullptr) {
   // (r5: 4-channel tasks -- 2304 half tasks, 4.5 per thread instead of 2.25 -- measured 0.5 us slower)
@@ -322,8 +357,8 @@ DEV void pool_emit(const bf16* cout, bf16* out, uint8_t* am, int tid, uint32_t* 
     uint4 o;
     uint32_t alo, ahi;
     pool_window(v, o, alo, ahi, bmax);
-    st_out16(out, (uint32_t)(q * 64 + c * 8) * 2, o);
-    st_out8(am, (uint32_t)(q * 64 + c * 8), make_uint2(alo, ahi));
+    if constexpr (ST_OUT) st_out16(out, (uint32_t)(q * 64 + c * 8) * 2, o);
+    if constexpr (ST_AM) st_out8(am, (uint32_t)(q * 64 + c * 8), make_uint2(alo, ahi));
     if (pad_lds) *reinterpret_cast<uint4*>(pad_lds + swzpad((py + 2) * (HO + 4) + px + 2, c)) = o;
   }
   if (vmax) *vmax = bmax;

@@ -39,6 +39,11 @@ the whole step is a static HIP graph and ``k`` consecutive steps -- across epoch
 one graph replay.  Any batch size works: the kernels run on the batch padded to the 16-row tile and
 the head gives padding rows zero loss weight (their gradients are exactly zero).
 
+Evaluation and inference (``evaluate``, ``infer``, ``infer_logits``) on a bf16 engine are one launch of
+k_cnn_infer (csrc/kernels/cnn_infer.hip): any uint8 images from pixels to logits, 16 images per
+persistent workgroup tile, reading the bf16 shadows as the last step left them and writing no training
+buffer.  ``evaluate(impl="batched")`` is the former walk through the training forward's kernels.
+
 Variants: every default below is the measured-fastest path of its configuration; the alternatives
 that stay are the bitwise references the tests compare against, selected with the ``variant``
 dict of the constructor (VARIANT_DEFAULTS).  Which path a configuration takes is decided by the pure
@@ -240,6 +245,7 @@ class FusedCifarEngine(FusedEngineBase):
         self._err_host = (torch.zeros(1, dtype=torch.int32).pin_memory() if on_gpu
                           else torch.zeros(1, dtype=torch.int32))
         self._dgrad_done = False
+        self._infer_scratch = {}       # infer(): grid size -> scratch slabs
         self.bwd_hand = torch.zeros(self.bwd_hand_words, dtype=torch.int32, device=dev)
 
         self.comm_stream = torch.cuda.Stream(device=dev) if self.dp else None
@@ -717,10 +723,64 @@ class FusedCifarEngine(FusedEngineBase):
             self.capture(steps_per_graph)
         return best
 
-    # --- evaluation -----------------------------------------------------------------------------
+    # --- inference / evaluation -----------------------------------------------------------------
     @torch.no_grad()
-    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0) -> float:
-        """Test accuracy over ``data`` (uint8 [N,32,32,3]) with the fused forward kernels."""
+    def infer(self, images_u8: torch.Tensor, labels: Optional[torch.Tensor] = None,
+              idx: Optional[torch.Tensor] = None, blocks: Optional[int] = None):
+        """Eval-mode forward of any uint8 [N,32,32,3] images (on any device) in ONE launch of k_cnn_infer
+        (csrc/kernels/cnn_infer.hip): (logits fp32 [n,10], pred int32 [n], correct int32 [n] or None
+        without ``labels``).  ``idx``: rows of ``images_u8`` to run (n = len(idx)), else all of them;
+        ``labels``: one per row of ``images_u8``; ``blocks``: workgroups of the persistent loop (None: one
+        per CU).  Reads the weights as the last step left them (the bf16 shadows, the fc1n slot of the
+        device step counter's parity), at the constructor's crop; writes no training buffer.  bf16
+        engines only: an fp8 engine keeps no current bf16 conv2 shadow (its SGD writes the e4m3 one)."""
+        if self.fp8:
+            raise RuntimeError("infer needs the bf16 conv2 shadow, which an fp8 engine does not keep current; "
+                               "use evaluate(impl='batched') / forward_logits")
+        dev = self.device
+        assert images_u8.dtype == torch.uint8 and tuple(images_u8.shape[1:]) == (32, 32, 3), images_u8.shape
+        images_u8 = images_u8.to(dev).contiguous()
+        if idx is not None:
+            idx = idx.to(dev, torch.int32).reshape(-1).contiguous()
+        n = images_u8.shape[0] if idx is None else idx.numel()
+        if labels is not None:
+            labels = labels.to(dev, torch.int32).reshape(-1).contiguous()
+        logits = torch.empty(n, 10, dtype=torch.float32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        correct = None if labels is None else torch.empty(n, dtype=torch.int32, device=dev)
+        # one [16][2304] bf16 slab of pooled activations per workgroup, cached by grid size
+        grid = max(1, min(-(-n // 16), int(blocks) if blocks else max(1, self.plan_inputs["cus"])))
+        scratch = self._infer_scratch.get(grid)
+        if scratch is None:
+            scratch = self._infer_scratch[grid] = torch.empty(grid, 16, 2304, dtype=torch.bfloat16, device=dev)
+        self.ops.cnn_infer(images_u8, idx, labels, self.cy, self.cx, self.w1f, self.w2f, self.fc1n, self.step_t,
+                           self.fc2t, self.fc3t, self.master, SEG_OFF, self.relu_logits, scratch, logits, pred,
+                           correct, int(blocks or 0))
+        return logits, pred, correct
+
+    def infer_logits(self, images_u8: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                     blocks: Optional[int] = None) -> torch.Tensor:
+        """Eval-mode logits fp32 [n,10] of uint8 images (see :meth:`infer`)."""
+        return self.infer(images_u8, None, idx, blocks)[0]
+
+    @torch.no_grad()
+    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0,
+                 impl: Optional[str] = None) -> float:
+        """Test accuracy over ``data`` (uint8 [N,32,32,3]).  ``impl="hip"``: the first ``max_batches *
+        batch`` images (0: all) through k_cnn_infer in one launch, the hits summed on the device;
+        ``impl="batched"``: batch by batch through the training forward's kernels (which writes the
+        activation buffers).  Default: "hip" on bf16 engines, "batched" on fp8 engines (see :meth:`infer`)."""
+        if impl is None:
+            impl = "batched" if self.fp8 else "hip"
+        if impl not in ("hip", "batched"):
+            raise ValueError(f"evaluate: impl must be 'hip' or 'batched', got {impl!r}")
+        if impl == "hip":
+            n = data.shape[0]
+            if max_batches:
+                n = min(n, max_batches * self.Bv)
+            if n == 0:
+                return 0.0
+            return int(self.infer(data[:n], labels[:n])[2].sum()) / n
         data = data.to(self.device).contiguous()
         labels = labels.to(self.device, torch.int32).contiguous()
         saved = (self.data, self.labels)
