@@ -797,14 +797,18 @@ void backward_fused(const Tensor& master, const Buf& buf, const Tensor& idx, con
 // N = data rows); writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels, one per
 // data row).  Reads the bf16 shadows, slot step & 1 of fc1n and the five bias views of master at `off`;
 // scratch: bf16 [S, 16, 2304] with S >= the launch's workgroups, min(ceil(N / 16), blocks or the CUs).
+// w2f8 (uint8 [64, 1600]) + scale_w (float [2]), both or neither: the fp8 variant -- conv2 on the e4m3
+// shadow with scale slot step & 1 and one activation scale per image; w2f is then not read.
 void cnn_infer(const Tensor& data, const c10::optional<Tensor>& idx, const c10::optional<Tensor>& labels, int64_t cy,
                int64_t cx, const Tensor& w1f, const Tensor& w2f, const Tensor& fc1n, const Tensor& step,
                const Tensor& fc2t, const Tensor& fc3t, const Tensor& master, at::IntArrayRef off, bool relu_logits,
                const Tensor& scratch, const Tensor& logits, const c10::optional<Tensor>& pred,
-               const c10::optional<Tensor>& correct, int64_t blocks) {
+               const c10::optional<Tensor>& correct, int64_t blocks, const c10::optional<Tensor>& w2f8,
+               const c10::optional<Tensor>& scale_w) {
   check_data(data);
   const int64_t rows = data.size(0), N = idx.has_value() ? idx->numel() : rows;
   TORCH_CHECK(rows >= 1 && rows < (1ll << 31) / 3072 * 16, "cnn_infer: data rows out of range");
+  TORCH_CHECK(w2f8.has_value() == scale_w.has_value(), "cnn_infer: w2f8 and scale_w go together (the fp8 variant)");
   TORCH_CHECK(N >= 1 && N < (1ll << 31) / 10, "cnn_infer: 1 <= N < 2^31 / 10");
   TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "cnn_infer: blocks must be >= 0 (0: one workgroup per CU)");
   TORCH_CHECK(cy >= 0 && cy <= 8 && cx >= 0 && cx <= 8, "crop offsets must be in [0,8]");
@@ -835,6 +839,12 @@ void cnn_infer(const Tensor& data, const c10::optional<Tensor>& idx, const c10::
   same_dev(fc2t, "fc2t"); same_dev(fc3t, "fc3t");
   a.w1f = w1f.data_ptr(); a.w2f = w2f.data_ptr(); a.fc1n = fc1n.data_ptr(); a.step = step.data_ptr<int64_t>();
   a.fc2t = fc2t.data_ptr(); a.fc3t = fc3t.data_ptr();
+  if (w2f8.has_value()) {                  // the fp8 variant: conv2 on the e4m3 shadow and its scale slots
+    check(*w2f8, "w2f8", at::kByte, {64, 1600});
+    check(*scale_w, "scale_w", at::kFloat, {2});
+    same_dev(*w2f8, "w2f8"); same_dev(*scale_w, "scale_w");
+    a.w2f8 = w2f8->data_ptr<uint8_t>(); a.scale_w = scale_w->data_ptr<float>();
+  }
   // the biases: views of the flat fp32 master (fc1's and fc2's are read as 16-B vectors)
   check_min(master, "master", at::kFloat, check_off(off));
   same_dev(master, "master");
@@ -899,7 +909,8 @@ TORCH_LIBRARY(dmlc, m) {
         "Tensor(g!) correct_part, Tensor(h!)? logits_out, int nvalid=-1, Tensor? step=None, Tensor(i!)? step_copy=None) -> ()");
   m.def("cnn_infer(Tensor data, Tensor? idx, Tensor? labels, int cy, int cx, Tensor w1f, Tensor w2f, Tensor fc1n, "
         "Tensor step, Tensor fc2t, Tensor fc3t, Tensor master, int[] off, bool relu_logits, Tensor(a!) scratch, "
-        "Tensor(b!) logits, Tensor(c!)? pred, Tensor(d!)? correct, int blocks=0) -> ()");
+        "Tensor(b!) logits, Tensor(c!)? pred, Tensor(d!)? correct, int blocks=0, Tensor? w2f8=None, "
+        "Tensor? scale_w=None) -> ()");
   // the engine-level ops: master, the named buffers, then what differs from call to call
   m.def("fc_chain(Tensor(a!) master, Dict(str, Tensor) buf, Tensor idx, Tensor? counter, int period, int[] off, "
         "float[] sched, int batch, float inv_batch, bool relu_logits, bool fuse_sgd, bool dw_tasks, bool dgrad, "

@@ -344,6 +344,11 @@ struct DmlcCnnInferArgs {
   int* pred;                         // nullable [N]: first maximum
   int* correct;                      // nullable [N]: pred == labels[row]
   int blocks;                        // workgroups; 0 = one per CU (never more than the ceil(N / 16) tiles)
+  // the fp8 variant (both set, or neither): conv2 runs on the e4m3 weights uint8 [64][1600] (the bytes the
+  // training forward reads; w2f is then not read) with the per-tensor scale scale_w[*step & 1], and
+  // quantises each image's pooled conv1 output with a power-of-two scale of that image alone
+  const uint8_t* w2f8;
+  const float* scale_w;              // float [2]
 };
 
 hipError_t dmlc_conv1_fwd(const DmlcConv1FwdArgs* a, hipStream_t s);

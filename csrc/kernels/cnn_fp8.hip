@@ -21,30 +21,17 @@
 // values the block just produced, rounded down to a power of two (r6); the quantised dY2 and its
 // scale are also stored (dy8out, sy_img) for the fp8 conv2 weight gradient (wgrad_core.h w2_fp8_main),
 // as the forward stores its quantised input and sx (x8out, sx_out).
-#include "conv_common.h"
+#include "fp8_common.h"
 
 namespace dmlc {
 
-typedef int fp8x32 __attribute__((ext_vector_type(8)));   // 32 packed e4m3 values (MFMA operand)
-
-constexpr int X8_BYTES = 256 * 64;            // [16x16 padded pixels][64 ch] fp8
-constexpr int W8_LD = 1792;                   // weight row stride (bytes): 26 taps x 64 used
+constexpr int W8_LD = 1792;                  // weight row stride (bytes): 26 taps x 64 used
 constexpr int W8_BYTES = 64 * W8_LD;
 constexpr size_t FP8_RED = X8_BYTES + W8_BYTES + 144 * 64 * 2;   // 8 wave maxima
 constexpr size_t FP8_LDS = FP8_RED + 64;
 static_assert(FP8_LDS <= 160 * 1024, "fp8 conv2 LDS");
 
-DEV int x8_addr(int P, int u) { return P * 64 + ((u ^ ((P >> 4) & 1)) << 4); }
 DEV int w8_addr(int row, int U) { return row * W8_LD + ((U ^ ((row & 1) | (((row >> 1) & 3) << 2))) << 4); }
-
-DEV f32x4 mfma_fp8(const fp8x32& a, const fp8x32& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
-}
-DEV fp8x32 lds_fp8x32(const uint8_t* lo, const uint8_t* hi) {
-  const uint4 a = *reinterpret_cast<const uint4*>(lo), b = *reinterpret_cast<const uint4*>(hi);
-  const fp8x32 r = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
-  return r;
-}
 
 // All of an fp8 [64 rows][1600] weight matrix -> LDS: 64 rows x 104 units of 16 B (units 100..103 =
 // the zero tap), 13 per thread in two rounds of up to 7 loads in flight.

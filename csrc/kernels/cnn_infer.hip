@@ -39,8 +39,45 @@
 // ds_read_b128 of a fragment takes 4 cycles -- conflict-free (an 8-element pad: 8 cycles, none: 32); the
 // B sub-tiles are the grouped GEMM's m-major image: 2 cycles per ds_read_b64_tr_b16, conflict-free.  The
 // stores: A rows 4 cycles (conflict-free), a B chunk's 16-B pieces 6.7 on average (2-way on a third).
+//
+// fp8 variant (k_cnn_infer<true>, for engines whose conv2 shadow is e4m3: a.w2f8 [64][1600] + a.scale_w):
+// the same launch with everything between pool1 and pool2 replaced; the conv1 front, the slab and the
+// whole fc phase are the code above, shared through the template parameter.
+//   scale      pool1 writes the bf16 p1 image as before and hands back each thread's largest pooled
+//              value; wave shuffles + 8 LDS words give the image's own amax.  sx = 2^k is the largest
+//              power of two with amax * sx <= 448 (k from amax's exponent and mantissa fields, clamped to
+//              +-126; amax = 0: sx = 1), so bf16 * sx is exact and a host reference reproduces the
+//              quantised bytes.  No scale depends on another image, on the tile or on N.  The weight scale
+//              is scale_w[*step & 1], read on the device like the fc1n parity; nothing but the outputs
+//              and the scratch is written.
+//   quantise   p1 (padded, halo included: zeros stay zeros) -> e4m3 through the hardware converter (RNE,
+//              saturating) into the padded [16x16][64] e4m3 image (16 KB, fp8_common.h x8_addr).
+//   conv2      v_mfma_scale_f32_16x16x128_f8f6f4, block scales 2^0, K = (tap, ci) in 13 chunks of 128 = two
+//              taps x 64 ci: 25 taps + one zero tap, 1/26 = 4 % of the MFMAs wasted (three chunks per
+//              kernel row would be 15 chunks, 17 %).  Both operands see the same k order (lane group g:
+//              tap 2c + (g >> 1), channels 32 (g & 1) .. + 31).  fp32 accumulators * 1 / (sx * sw) + bias,
+//              ReLU, bf16, pool2 into the slab row as above.
+//   weights    streamed e4m3 slices.  The whole e4m3 matrix is 13 chunk blocks [64 rows][128 B] = 104 KB,
+//              and once p1 is quantised [0, 112 KB) is free, so every block has a home of its own and no
+//              buffer is reused inside an image: slice 0 (chunks 0-3) and chunk 12 are requested into
+//              registers under the previous image's pool2 (as kernel row 0 above) and stored after
+//              pool1; slice 1 (chunks 4-7) is copied by LDS-DMA under slice 0's MFMAs, slice 2 (chunks
+//              8-11) under slice 1's, each awaited (vmcnt(0) + barrier) at its predecessor's end: two
+//              barriers inside the core.  Chunk 12's zero tap is stored as zeros (only 64 B of its 128
+//              exist per row in memory).  Per image 104 KB of weights cross L2 -> CU instead of 200 KB.
+// LDS, fp8 conv phase (same 154,624 B):
+//   [0, 32 KB) slice 0   [32, 40 KB) chunk 12   [40, 72 KB) slice 1   [72, 104 KB) slice 2 (over the bf16
+//   p1 image at [80, 112 KB), free once quantised)   [112, 130 KB) conv2 output
+//   [130, 146 KB) e4m3 input, then 8 wave maxima (the conv1 input region, free after conv1's MFMAs)
+// Bank model (tools/lds_banks.py cycles(), 4 = conflict-free): a weight row's eight 16-B units are XORed
+// with (row >> 1 & 1) | (row >> 3 & 1) << 2: every A half-fragment read 4 cycles (no key 16, the key
+// (row >> 1) & 7 8); the e4m3 input under x8_addr with 4x4-pixel tiles: every B read 4 cycles over all 9
+// tiles x 25 taps; the quantiser's p1 reads 4 cycles, its 8-B stores 2 (ds_write_b64 lane groups).
+// Per chunk a wave reads 2 A + 2-3 B fragments of 2 KB for 4-5 MFMAs of 32 cycles: 72 KB per chunk and CU
+// = 288 LDS cycles against 288 MFMA cycles per SIMD (bf16: 36 KB per 144 MFMA cycles, 50 chunks).
 #include "conv2_core.h"
 #include "fc_common.h"
+#include "fp8_common.h"
 
 namespace dmlc {
 
@@ -82,6 +119,140 @@ DEV void ci_store_relu(bf16* h, const f32x4& acc, const float4& b) {
                                         fmaxf(acc[2] + b.z, 0.f), fmaxf(acc[3] + b.w, 0.f));
 }
 
+// ---------------------------------------------------------------------------------------------
+// fp8 variant (k_cnn_infer<true>): conv2 on v_mfma_scale_f32_16x16x128_f8f6f4, see the header comment.
+constexpr int F8_CHUNK = 64 * 128;             // one K chunk (two taps x 64 ci) of all 64 weight rows, bytes
+constexpr int F8_SLICE = 4 * F8_CHUNK;         // 32 KB
+constexpr int F8_S0 = 0, F8_C12 = F8_S0 + F8_SLICE, F8_S1 = F8_C12 + F8_CHUNK, F8_S2 = F8_S1 + F8_SLICE;
+constexpr int F8_X8 = (int)C12_XIN1, F8_RED = F8_X8 + X8_BYTES;
+static_assert(F8_S1 + F8_SLICE <= (int)C12_XIN2, "slices 0, 1 and chunk 12 lie in the conv1 output region");
+static_assert(F8_S2 + F8_SLICE <= (int)C12_OUT2, "slice 2 ends inside the bf16 p1 image, before conv2's output");
+static_assert(F8_RED + 8 * 4 <= (int)C12_LDS && F8_X8 % 16 == 0, "e4m3 input + wave maxima in the conv1 input region");
+
+// XOR key of a weight row's eight 16-B units inside a chunk block [64 rows][128 B]
+DEV int w8k(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 2); }
+// byte offset in w2f8 [64][1600] of piece P (= LDS unit P of the slice buffer) of slice s < 3
+DEV int f8_src(int s, int P) {
+  const int cb = P >> 9, row = (P >> 3) & 63, lc = (P & 7) ^ w8k(row);
+  return row * 1600 + (4 * s + cb) * 128 + lc * 16;
+}
+// slice s (1 or 2) -> its LDS home by LDS-DMA: 32 wave-instructions of 1 KB, 4 per wave
+DEV void f8_dma(const uint8_t* Wg, int s, uint8_t* buf, int w, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int j = w * 4 + i;                   // wave-uniform
+    __builtin_amdgcn_global_load_lds(Wg + f8_src(s, j * 64 + lane), (LDS_AS void*)(buf + j * 1024), 16, 0, 0);
+  }
+}
+// Slice 0 (a..d) and chunk 12 (e: tap 24 + the zero tap, of which only the first 64 B of a row exist
+// in memory -- the other units are stored as zeros) through registers, as conv2_core.h ws_fetch / ws_put.
+DEV Slice5 f8_fetch(const uint8_t* Wg, int w, int lane) {
+  const int t = w * 64 + lane, row = t >> 3, lc = (t & 7) ^ w8k(row);
+  const uint4 e = *reinterpret_cast<const uint4*>(Wg + row * 1600 + 1536 + (lc & 3) * 16);
+  const uint4* src = reinterpret_cast<const uint4*>(Wg);
+  return Slice5{src[f8_src(0, (w * 4 + 0) * 64 + lane) >> 4], src[f8_src(0, (w * 4 + 1) * 64 + lane) >> 4],
+                src[f8_src(0, (w * 4 + 2) * 64 + lane) >> 4], src[f8_src(0, (w * 4 + 3) * 64 + lane) >> 4],
+                lc < 4 ? e : make_uint4(0u, 0u, 0u, 0u)};
+}
+DEV void f8_put(uint8_t* s0, uint8_t* c12, int w, int lane, Slice5 v) {
+  uint4* p = reinterpret_cast<uint4*>(s0) + w * 256 + lane;
+  p[0] = v.a; p[64] = v.b; p[128] = v.c; p[192] = v.d;
+  reinterpret_cast<uint4*>(c12)[w * 64 + lane] = v.e;
+}
+// A fragment's two 16-B halves, read as vectors: a load of the uint4 STRUCT (fp8_common.h lds_fp8x32) is
+// an aggregate copy and carries no type information, and hipcc's waitcnt pass then makes the first such
+// LDS read behind an LDS-DMA wait vmcnt(0) for it -- the next slice's copy would not overlap the MFMAs.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+DEV fp8x32 lds_f8(const uint8_t* lo, const uint8_t* hi) {
+  return __builtin_shufflevector(*reinterpret_cast<const i32x4*>(lo), *reinterpret_cast<const i32x4*>(hi), 0, 1, 2, 3,
+                                 4, 5, 6, 7);
+}
+constexpr int f8_chunk_off(int c) {
+  return c < 4 ? F8_S0 + c * F8_CHUNK : c < 8 ? F8_S1 + (c - 4) * F8_CHUNK : c < 12 ? F8_S2 + (c - 8) * F8_CHUNK : F8_C12;
+}
+constexpr int f8_tap_off(int tap) { return ((tap / 5) * 16 + tap % 5) * 64; }   // padded-pixel byte offset of a tap
+
+// The MFMAs of one image.  Tile ownership is conv2_core's: wave (cp, pg) owns c_out tiles 2cp, 2cp + 1 of
+// the pixel tiles pg and pg + 4, waves 0-3 also pixel tile 8 for the one c_out tile 2cp + pg (9 of the
+// 36 tile units per SIMD) -- but a pixel tile is a 4x4 block of the 12x12 output, which is what makes
+// the e4m3 input image's reads conflict-free under x8_addr's row-parity key.  Lane group g holds
+// k = 32g .. 32g + 31 of a chunk: tap 2c + (g >> 1), channels 32 (g & 1) .. + 31, for the weight row and
+// the pixel alike.  On entry slice 0 and chunk 12 are in LDS behind a barrier; slice s + 1 is requested
+// by LDS-DMA before slice s's MFMAs and awaited (vmcnt(0) + barrier) behind them.
+template <bool EXTRA>
+DEV void conv2_core_f8(const uint8_t* Wg, char* smem, f32x4 (&acc)[2][2], f32x4& accx, int pg, int cp, int xsel,
+                       int g, int li, int w, int lane) {
+  constexpr int NPX = EXTRA ? 3 : 2;
+  const uint8_t* lds = reinterpret_cast<const uint8_t*>(smem);
+  const int u = 2 * (g & 1), gh = g >> 1;
+  int xb[NPX];                                 // pixel byte address with the unit XOR of tap (0, 0)
+#pragma unroll
+  for (int t = 0; t < NPX; ++t) {
+    const int T = t < 2 ? pg + 4 * t : 8, ty = T / 3, tx = T - ty * 3;
+    const int pb = (4 * ty + (li >> 2)) * 16 + 4 * tx + (li & 3);
+    xb[t] = F8_X8 + x8_addr(pb, u);
+  }
+  const int ao = (32 * cp + li) * 128 + (((2 * g) ^ w8k(li)) << 4);   // (w8k(row) = w8k(li): bits 1 and 3)
+#pragma unroll
+  for (int t = 0; t < 2; ++t) { acc[0][t] = zero4(); acc[1][t] = zero4(); }
+  accx = zero4();
+  f8_dma(Wg, 1, reinterpret_cast<uint8_t*>(smem) + F8_S1, w, lane);
+  // chunk c: 2 A + NPX B fragments of two 16-B reads each (the halves differ in address bit 4 only: the
+  // keys XOR whole units and a lane's first unit is even); taps past 24 read tap 24 against zero weights
+  auto load_chunk = [&](int c, fp8x32& a0, fp8x32& a1, fp8x32 (&bx)[NPX]) {
+    const int wo = f8_chunk_off(c) + ao;
+    a0 = lds_f8(lds + wo, lds + (wo ^ 16));
+    a1 = lds_f8(lds + wo + 16 * 128, lds + ((wo + 16 * 128) ^ 16));
+    const int t0 = 2 * c, t1 = 2 * c + 1 < 25 ? 2 * c + 1 : 24;
+    const int xoff = gh ? f8_tap_off(t1) : f8_tap_off(t0);
+    const int flip = (gh ? (t1 / 5) & 1 : (t0 / 5) & 1) << 4;         // the tap's kernel row flips the parity key
+#pragma unroll
+    for (int t = 0; t < NPX; ++t) {
+      const int ad = (xb[t] ^ flip) + xoff;
+      bx[t] = lds_f8(lds + ad, lds + (ad ^ 16));
+    }
+  };
+  fp8x32 A0[2], A1[2], BX[2][NPX];
+  load_chunk(0, A0[0], A1[0], BX[0]);
+#pragma unroll
+  for (int c = 0; c < 13; ++c) {
+    const int cur = c & 1;
+    const bool last_of_slice = c == 3 || c == 7;         // chunk c + 1 lies in a slice still in flight
+    wait_lds();
+    __builtin_amdgcn_sched_barrier(0);
+    if (c + 1 < 13 && !last_of_slice) load_chunk(c + 1, A0[cur ^ 1], A1[cur ^ 1], BX[cur ^ 1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      acc[0][t] = mfma_fp8(A0[cur], BX[cur][t], acc[0][t]);
+      acc[1][t] = mfma_fp8(A1[cur], BX[cur][t], acc[1][t]);
+    }
+    if constexpr (EXTRA) accx = mfma_fp8(xsel ? A1[cur] : A0[cur], BX[cur][NPX - 1], accx);
+    __builtin_amdgcn_sched_barrier(0);
+    if (last_of_slice) {
+      __syncthreads();                                   // (waits vmcnt(0): the next slice has landed)
+      if (c == 3) f8_dma(Wg, 2, reinterpret_cast<uint8_t*>(smem) + F8_S2, w, lane);
+      load_chunk(c + 1, A0[cur ^ 1], A1[cur ^ 1], BX[cur ^ 1]);
+    }
+  }
+}
+
+template <class F>
+DEV void conv2_tiles_f8(const uint8_t* Wg, char* smem, int w, int g, int li, int lane, F&& fn) {
+  const int cp = w & 1, pg = w >> 1;
+  f32x4 acc[2][2], accx;
+  if (w < 4) {
+    conv2_core_f8<true>(Wg, smem, acc, accx, pg, cp, pg, g, li, w, lane);
+    fn(2 * cp + pg, 8, accx);
+  } else {
+    conv2_core_f8<false>(Wg, smem, acc, accx, pg, cp, 0, g, li, w, lane);
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t) { fn(2 * cp, pg + 4 * t, acc[0][t]); fn(2 * cp + 1, pg + 4 * t, acc[1][t]); }
+}
+
+// F8: conv2 in e4m3 (a.w2f8, a.scale_w) instead of bf16 (a.w2f); everything else is shared.
+template <bool F8>
 __global__ __launch_bounds__(NT, 1) void k_cnn_infer(DmlcCnnInferArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // conv map (as k_conv12_fwd)
@@ -115,6 +286,10 @@ __global__ __launch_bounds__(NT, 1) void k_cnn_infer(DmlcCnnInferArgs a) {
   DmlcConv1FwdArgs c1 = {};                  // the launch-wide centre crop: no augmentation word
   c1.cy = a.cy; c1.cx = a.cx;
   const bf16* W2 = reinterpret_cast<const bf16*>(a.w2f);
+  const uint8_t* W8 = a.w2f8;
+  // 1 / sw of the e4m3 weights: the scale slot of the step counter's parity, as the fc1n slot below
+  float rsw = 1.f;
+  if constexpr (F8) rsw = 1.f / a.scale_w[*a.step & 1];
   const bf16* W1 = reinterpret_cast<const bf16*>(a.fc1n) + ((*a.step & 1) ? (size_t)CI_K1 * CI_N1 : 0);
   bf16* slab = reinterpret_cast<bf16*>(a.scratch) + (size_t)blockIdx.x * CI_TM * CI_K1;
   // image n of the launch (clamped: the request past the workgroup's last image re-reads a valid one)
@@ -126,7 +301,12 @@ __global__ __launch_bounds__(NT, 1) void k_cnn_infer(DmlcCnnInferArgs a) {
     return reinterpret_cast<const uint4*>(a.data + (size_t)row_of(n) * 3072)[min(t, 191)];
   };
   uint4 rawv = fetch_raw(blockIdx.x * CI_TM, tid);
-  Slice5 s0v = ws_fetch(W2, 0, w, lane);     // conv2 kernel row 0: in flight during conv1 + pool1
+  // conv2 kernel row 0 (fp8: slice 0 and chunk 12): in flight during conv1 + pool1
+  auto fetch_s0 = [&](int l) {
+    if constexpr (F8) return f8_fetch(W8, w, l);
+    else return ws_fetch(W2, 0, w, l);
+  };
+  Slice5 s0v = fetch_s0(lane);
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int nv = min(CI_TM, a.N - tile * CI_TM);
@@ -157,17 +337,54 @@ __global__ __launch_bounds__(NT, 1) void k_cnn_infer(DmlcCnnInferArgs a) {
             store_relu_tile(cout, (pq * 9 + t) * 16 + ili, 32 * cp + 16 * h + 4 * ig, acc[h][t], b4[h]);
       }
       lds_barrier();
-      pool_emit<24, false, false>(cout, nullptr, nullptr, it, nullptr, xin2);
-      lds_barrier();                                       // conv2 input complete; conv1 region free
-      ws_put(ws, w, il, s0v);                              // published by the core's first barrier
-      conv2_tiles(W2, xin2, ws, w, ig, ili, it, ws, [&](int ct, int t, const f32x4& acc) {
-        store_relu_tile(cout2, 16 * t + ili, 16 * ct + 4 * ig, acc, c2b[ct]);
-      });
+      if constexpr (!F8) {
+        pool_emit<24, false, false>(cout, nullptr, nullptr, it, nullptr, xin2);
+        lds_barrier();                                     // conv2 input complete; conv1 region free
+        ws_put(ws, w, il, s0v);                            // published by the core's first barrier
+        conv2_tiles(W2, xin2, ws, w, ig, ili, it, ws, [&](int ct, int t, const f32x4& acc) {
+          store_relu_tile(cout2, 16 * t + ili, 16 * ct + 4 * ig, acc, c2b[ct]);
+        });
+      } else {
+        // pool1 -> the bf16 p1 image as above, and this thread's largest pooled value (as bf16 bits: the
+        // values are >= 0, so their bits order like them); the image's own amax in-block
+        uint32_t bm = 0;
+        pool_emit<24, false, false>(cout, nullptr, nullptr, it, &bm, xin2);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bm = max(bm, (uint32_t)__shfl_xor((int)bm, o));
+        uint32_t* red = reinterpret_cast<uint32_t*>(smem + F8_RED);
+        if (il == 0) red[w] = bm;
+        lds_barrier();                                     // p1 and the wave maxima complete; conv1 region free
+        f8_put(reinterpret_cast<uint8_t*>(smem) + F8_S0, reinterpret_cast<uint8_t*>(smem) + F8_C12, w, il, s0v);
+        uint32_t am = red[0];
+#pragma unroll
+        for (int j = 1; j < NT / 64; ++j) am = max(am, red[j]);
+        // sx = 2^k, the largest power of two with amax * sx <= 448 = 1.75 * 2^8, from amax's bf16 fields
+        // (exact: no log2), k within +-126; amax = 0: sx = 1.  bf16 * sx is then exact in fp32.
+        const int ex = (int)(am >> 7), mant = (int)(am & 0x7f);
+        const int k = am ? min(max(8 - (ex - 127) - (mant > 0x60 ? 1 : 0), -126), 126) : 0;
+        const float sx = __uint_as_float((uint32_t)(127 + k) << 23);
+        const float inv = __uint_as_float((uint32_t)(127 - k) << 23) * rsw;   // 1 / (sx * sw)
+        uint8_t* x8 = reinterpret_cast<uint8_t*>(smem) + F8_X8;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                      // p1 (halo included: zeros) -> e4m3, 8 channels a task
+          const int s = it + j * NT, pix = s >> 3, c = s & 7;
+          const uint4 v = *reinterpret_cast<const uint4*>(xin2 + swzpad(pix, c));
+          const uint32_t lo = pk_fp8x4(bf16_lo(v.x) * sx, bf16_hi(v.x) * sx, bf16_lo(v.y) * sx, bf16_hi(v.y) * sx);
+          const uint32_t hi = pk_fp8x4(bf16_lo(v.z) * sx, bf16_hi(v.z) * sx, bf16_lo(v.w) * sx, bf16_hi(v.w) * sx);
+          *reinterpret_cast<uint2*>(x8 + x8_addr(pix, c >> 1) + (c & 1) * 8) = make_uint2(lo, hi);
+        }
+        lds_barrier();                                     // e4m3 input, slice 0, chunk 12 complete; p1 free
+        conv2_tiles_f8(W8, smem, w, ig, ili, il, [&](int ct, int T, f32x4 acc) {
+          acc[0] *= inv; acc[1] *= inv; acc[2] *= inv; acc[3] *= inv;
+          const int ty = T / 3, tx = T - ty * 3;
+          store_relu_tile(cout2, (4 * ty + (ili >> 2)) * 12 + 4 * tx + (ili & 3), 16 * ct + 4 * ig, acc, c2b[ct]);
+        });
+      }
       __syncthreads();
       // the next image of this workgroup (the next tile's first after the tile's last): its pixels and
       // conv2 kernel row 0 are in flight during pool2 (and, at a tile's end, the fc phase)
       rawv = fetch_raw(i + 1 < nv ? tile * CI_TM + i + 1 : (tile + (int)gridDim.x) * CI_TM, it);
-      s0v = ws_fetch(W2, 0, w, il);
+      s0v = fetch_s0(il);
       pool_emit<12, true, false>(cout2, slab + i * CI_K1, nullptr, it);
     }
     wait_vm_all();                         // every wave's slab stores acknowledged by L2 ...
@@ -306,12 +523,18 @@ hipError_t dmlc_cnn_infer_grid(int N, int blocks, int* grid) {
 
 hipError_t dmlc_cnn_infer(const DmlcCnnInferArgs* a, hipStream_t s) {
   if (a->N < 1 || a->nrows < 1 || a->blocks < 0 || (a->correct && !a->labels)) return hipErrorInvalidValue;
+  if (!a->w2f8 != !a->scale_w || (!a->w2f8 && !a->w2f)) return hipErrorInvalidValue;
   int grid = 0;
   const hipError_t e = dmlc_cnn_infer_grid(a->N, a->blocks, &grid);
   if (e != hipSuccess) return e;
   if (a->scratch_slabs < grid) return hipErrorInvalidValue;   // one slab per workgroup
-  DMLC_LDS_OPTIN(&k_cnn_infer, CI_LDS);
-  hipLaunchKernelGGL(k_cnn_infer, dim3(grid), dim3(NT), CI_LDS, s, *a);
+  if (a->w2f8) {                           // the fp8 variant: e4m3 conv2 weights + their scale slots
+    DMLC_LDS_OPTIN(&k_cnn_infer<true>, CI_LDS);
+    hipLaunchKernelGGL(k_cnn_infer<true>, dim3(grid), dim3(NT), CI_LDS, s, *a);
+  } else {
+    DMLC_LDS_OPTIN(&k_cnn_infer<false>, CI_LDS);
+    hipLaunchKernelGGL(k_cnn_infer<false>, dim3(grid), dim3(NT), CI_LDS, s, *a);
+  }
   return hipGetLastError();
 }
 

@@ -39,10 +39,12 @@ the whole step is a static HIP graph and ``k`` consecutive steps -- across epoch
 one graph replay.  Any batch size works: the kernels run on the batch padded to the 16-row tile and
 the head gives padding rows zero loss weight (their gradients are exactly zero).
 
-Evaluation and inference (``evaluate``, ``infer``, ``infer_logits``) on a bf16 engine are one launch of
-k_cnn_infer (csrc/kernels/cnn_infer.hip): any uint8 images from pixels to logits, 16 images per
-persistent workgroup tile, reading the bf16 shadows as the last step left them and writing no training
-buffer.  ``evaluate(impl="batched")`` is the former walk through the training forward's kernels.
+Evaluation and inference (``evaluate``, ``infer``, ``infer_logits``) are one launch of k_cnn_infer
+(csrc/kernels/cnn_infer.hip): any uint8 images from pixels to logits, 16 images per persistent
+workgroup tile, reading the bf16 shadows as the last step left them and writing no training buffer; on
+an fp8 engine the kernel's fp8 variant runs conv2 on the e4m3 shadow with one activation scale per
+image.  ``evaluate(impl="batched")`` is the former walk through the training forward's kernels (still
+the default of ``evaluate`` on fp8 engines).
 
 Variants: every default below is the measured-fastest path of its configuration; the alternatives
 that stay are the bitwise references the tests compare against, selected with the ``variant``
@@ -732,11 +734,12 @@ class FusedCifarEngine(FusedEngineBase):
         without ``labels``).  ``idx``: rows of ``images_u8`` to run (n = len(idx)), else all of them;
         ``labels``: one per row of ``images_u8``; ``blocks``: workgroups of the persistent loop (None: one
         per CU).  Reads the weights as the last step left them (the bf16 shadows, the fc1n slot of the
-        device step counter's parity), at the constructor's crop; writes no training buffer.  bf16
-        engines only: an fp8 engine keeps no current bf16 conv2 shadow (its SGD writes the e4m3 one)."""
-        if self.fp8:
-            raise RuntimeError("infer needs the bf16 conv2 shadow, which an fp8 engine does not keep current; "
-                               "use evaluate(impl='batched') / forward_logits")
+        device step counter's parity), at the constructor's crop; writes no training buffer.  An fp8 engine
+        keeps no current bf16 conv2 shadow (its SGD writes the e4m3 one), so it runs the kernel's fp8
+        variant: conv2 on the e4m3 MFMA with ``w2f8[0]``, the bytes its training forward reads, the weight
+        scale ``scale_w[step & 1]`` read on the device, and one power-of-two activation scale per image
+        (the training forward's is per batch), so an image's logits do not depend on its neighbours."""
+        f8 = (self.w2f8[0], self.scale_w) if self.fp8 else (None, None)
         dev = self.device
         assert images_u8.dtype == torch.uint8 and tuple(images_u8.shape[1:]) == (32, 32, 3), images_u8.shape
         images_u8 = images_u8.to(dev).contiguous()
@@ -755,7 +758,7 @@ class FusedCifarEngine(FusedEngineBase):
             scratch = self._infer_scratch[grid] = torch.empty(grid, 16, 2304, dtype=torch.bfloat16, device=dev)
         self.ops.cnn_infer(images_u8, idx, labels, self.cy, self.cx, self.w1f, self.w2f, self.fc1n, self.step_t,
                            self.fc2t, self.fc3t, self.master, SEG_OFF, self.relu_logits, scratch, logits, pred,
-                           correct, int(blocks or 0))
+                           correct, int(blocks or 0), *f8)
         return logits, pred, correct
 
     def infer_logits(self, images_u8: torch.Tensor, idx: Optional[torch.Tensor] = None,
@@ -769,7 +772,9 @@ class FusedCifarEngine(FusedEngineBase):
         """Test accuracy over ``data`` (uint8 [N,32,32,3]).  ``impl="hip"``: the first ``max_batches *
         batch`` images (0: all) through k_cnn_infer in one launch, the hits summed on the device;
         ``impl="batched"``: batch by batch through the training forward's kernels (which writes the
-        activation buffers).  Default: "hip" on bf16 engines, "batched" on fp8 engines (see :meth:`infer`)."""
+        activation buffers; on an fp8 engine its conv2 quantises with one activation scale per batch).
+        Default: "hip" on bf16 engines, "batched" on fp8 engines, where "hip" runs the kernel's fp8 variant
+        (see :meth:`infer`)."""
         if impl is None:
             impl = "batched" if self.fp8 else "hip"
         if impl not in ("hip", "batched"):
