@@ -130,9 +130,87 @@ Tensor f32_colsum(const Tensor& x) {
   return out;
 }
 
+// The whole eval-mode forward in true fp32, one launch (f32_infer.hip): image i is data[idx[i]] (idx None:
+// data[i], N = data rows); writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels,
+// one per data row).  flat: the model's fp32 parameter buffer, off: the element offsets of its ten TF-layout
+// tensors (conv1 kernel, bias, conv2 kernel, bias, fc1 weight, bias, fc2, fc3 likewise); scratch: fp32
+// [S, 16, 2304] with S >= the launch's workgroups, min(ceil(N / 16), blocks or the CUs).
+void f32_cnn_infer(const Tensor& data, const c10::optional<Tensor>& idx, const c10::optional<Tensor>& labels,
+                   int64_t cy, int64_t cx, const Tensor& flat, at::IntArrayRef off, bool relu_logits,
+                   const Tensor& scratch, const Tensor& logits, const c10::optional<Tensor>& pred,
+                   const c10::optional<Tensor>& correct, int64_t blocks) {
+  check_data(data);
+  const int64_t rows = data.size(0), N = idx.has_value() ? idx->numel() : rows;
+  TORCH_CHECK(rows >= 1 && rows < (1ll << 31) / 3072 * 16, "f32_cnn_infer: data rows out of range");
+  TORCH_CHECK(N >= 1 && N < (1ll << 31) / 10, "f32_cnn_infer: 1 <= N < 2^31 / 10");
+  TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "f32_cnn_infer: blocks must be >= 0 (0: one workgroup per CU)");
+  TORCH_CHECK(cy >= 0 && cy <= 8 && cx >= 0 && cx <= 8, "f32_cnn_infer: crop offsets must be in [0,8]");
+  const auto same_dev = [&](const Tensor& t, const char* n) {
+    TORCH_CHECK(t.device() == data.device(), "f32_cnn_infer: ", n, " must be on data's device");
+  };
+  DmlcF32InferArgs a;
+  memset(&a, 0, sizeof(a));
+  a.data = data.data_ptr<uint8_t>(); a.nrows = (int)rows;
+  a.N = (int)N; a.cy = (int)cy; a.cx = (int)cx; a.blocks = (int)blocks; a.relu_logits = relu_logits ? 1 : 0;
+  if (idx.has_value()) {
+    check_numel(*idx, "idx", at::kInt, N);
+    same_dev(*idx, "idx");
+    a.idx = idx->data_ptr<int>();
+  }
+  if (labels.has_value()) {
+    check_numel(*labels, "labels", at::kInt, rows);
+    same_dev(*labels, "labels");
+    a.labels = labels->data_ptr<int>();
+  }
+  // the ten parameter tensors: in order, inside flat, each on a 16-byte boundary (the kernel reads the
+  // biases as 16-B vectors)
+  static const int64_t numel[10] = {75 * 64, 64, 1600 * 64, 64, 2304 * 384, 384, 384 * 192, 192, 192 * 10, 10};
+  f32_in(flat, "flat", 1);
+  same_dev(flat, "flat");
+  TORCH_CHECK(off.size() == 10, "f32_cnn_infer: off must hold the 10 parameter offsets, got ", off.size());
+  int64_t end = 0;
+  for (int i = 0; i < 10; ++i) {
+    TORCH_CHECK(off[i] >= end && off[i] % 4 == 0, "f32_cnn_infer: parameter offset ", i, " (", off[i],
+                ") overlaps its predecessor or is not 16-byte aligned");
+    end = off[i] + numel[i];
+  }
+  TORCH_CHECK(flat.numel() >= end, "f32_cnn_infer: flat has ", flat.numel(), " elements, the parameters need ", end);
+  const float* f = flat.data_ptr<float>();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(f) % 16 == 0, "f32_cnn_infer: flat must be 16-byte aligned");
+  a.w1 = f + off[0]; a.b1 = f + off[1]; a.w2 = f + off[2]; a.b2 = f + off[3]; a.fw1 = f + off[4]; a.fb1 = f + off[5];
+  a.fw2 = f + off[6]; a.fb2 = f + off[7]; a.fw3 = f + off[8]; a.fb3 = f + off[9];
+  const c10::DeviceGuard guard(data.device());
+  int grid = 0;
+  CHECK_HIP(dmlc_f32_infer_grid((int)N, (int)blocks, &grid));
+  dev(scratch, "scratch");
+  same_dev(scratch, "scratch");
+  TORCH_CHECK(scratch.scalar_type() == at::kFloat && scratch.dim() == 3 && scratch.size(1) == 16 &&
+                  scratch.size(2) == 2304 && scratch.size(0) >= grid,
+              "f32_cnn_infer: scratch must be fp32 [S >= ", grid, " workgroups, 16, 2304], got ", scratch.sizes());
+  a.scratch = scratch.data_ptr<float>(); a.scratch_slabs = (int)std::min<int64_t>(scratch.size(0), 1 << 30);
+  check(logits, "logits", at::kFloat, {N, 10});
+  same_dev(logits, "logits");
+  a.logits = logits.data_ptr<float>();
+  if (pred.has_value()) {
+    check_numel(*pred, "pred", at::kInt, N);
+    same_dev(*pred, "pred");
+    a.pred = pred->data_ptr<int>();
+  }
+  if (correct.has_value()) {
+    TORCH_CHECK(labels.has_value(), "f32_cnn_infer: correct needs labels");
+    check_numel(*correct, "correct", at::kInt, N);
+    same_dev(*correct, "correct");
+    a.correct = correct->data_ptr<int>();
+  }
+  CHECK_HIP(dmlc_f32_infer(&a, stream_of(data)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(dmlc, m) {
+  m.def("f32_cnn_infer(Tensor data, Tensor? idx, Tensor? labels, int cy, int cx, Tensor flat, int[] off, "
+        "bool relu_logits, Tensor(a!) scratch, Tensor(b!) logits, Tensor(c!)? pred, Tensor(d!)? correct, "
+        "int blocks=0) -> ()");
   m.def("f32_gemm(Tensor a, Tensor b, Tensor? bias, bool ta, bool tb, bool relu) -> Tensor");
   m.def("f32_conv_gemm(Tensor x, Tensor w, Tensor? bias, bool ta, bool ones) -> Tensor");
   m.def("f32_im2col(Tensor x, int kh, int kw, int pad) -> Tensor");
@@ -146,4 +224,5 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_im2col", &f32_im2col);
   m.impl("f32_col2im", &f32_col2im);
   m.impl("f32_colsum", &f32_colsum);
+  m.impl("f32_cnn_infer", &f32_cnn_infer);
 }

@@ -31,4 +31,28 @@ hipError_t dmlc_f32_col2im(const float* dcols, float* dx, int B, int H, int W, i
 // out[N] = sum over the M rows of x[M][N], in a fixed order (ws: >= splits * N floats).
 hipError_t dmlc_f32_colsum(const float* x, float* out, float* ws, int M, int N, int splits, hipStream_t s);
 
+// k_cnn_infer_f32 (csrc/kernels/f32_infer.hip): the eval-mode forward of the CIFAR-10 CNN in true fp32,
+// uint8 pixels to fp32 logits in one launch.  Image i of the launch is data[idx[i]] (idx null: data[i]);
+// the weights are the TF-layout views of the model's flat fp32 parameter buffer (every pointer 16-byte
+// aligned).  scratch: fp32 [scratch_slabs][16][2304], one slab per workgroup; pred / correct optional
+// (correct needs labels, one per data row).  blocks: workgroups of the persistent loop, 0 = one per CU.
+typedef struct {
+  const uint8_t* data;       // [nrows][32][32][3]
+  const int* idx;            // [N] or null
+  const int* labels;         // [nrows] or null
+  const float *w1, *b1;      // [75][64], [64]
+  const float *w2, *b2;      // [1600][64], [64]
+  const float *fw1, *fb1;    // [2304][384], [384]
+  const float *fw2, *fb2;    // [384][192], [192]
+  const float *fw3, *fb3;    // [192][10], [10]
+  float* scratch;
+  float* logits;             // [N][10]
+  int* pred;                 // [N] or null
+  int* correct;              // [N] or null
+  int N, nrows, cy, cx, relu_logits, blocks, scratch_slabs;
+} DmlcF32InferArgs;
+// the launch's grid: min(ceil(N / 16), blocks or the device's CU count)
+hipError_t dmlc_f32_infer_grid(int N, int blocks, int* grid);
+hipError_t dmlc_f32_infer(const DmlcF32InferArgs* a, hipStream_t s);
+
 }  // extern "C"

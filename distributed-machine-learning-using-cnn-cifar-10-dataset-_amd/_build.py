@@ -38,10 +38,11 @@ VARIANT, VARIANT_FLAGS = (_VAR.split(":", 1)[0], _VAR.split(":", 1)[1].split()) 
 _SUFFIX = "_timing" if TIMING else (f"_{VARIANT}" if VARIANT else "")
 HIP_LIB = os.path.join(LIB_DIR, f"libdmlc_hip{_SUFFIX}.so")
 RT_LIB = os.path.join(LIB_DIR, "_dmlc_rt" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
-# extra hipcc flags of single kernel files.  resnet_infer.hip, cnn_infer.hip: scalar fp32 VALU only (no
-# packed fp32 pairs), so an image's logits cannot depend on how the compiler paired the epilogue's values
+# extra hipcc flags of single kernel files.  resnet_infer.hip, cnn_infer.hip, f32_infer.hip: scalar fp32
+# VALU only (no packed fp32 pairs), so an image's logits cannot depend on how the compiler paired the
+# epilogue's values
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_FILE_FLAGS = {"resnet_infer.hip": _NO_PK_F32, "cnn_infer.hip": _NO_PK_F32}
+HIP_FILE_FLAGS = {"resnet_infer.hip": _NO_PK_F32, "cnn_infer.hip": _NO_PK_F32, "f32_infer.hip": _NO_PK_F32}
 
 
 def _torch_paths():

@@ -20,7 +20,12 @@ import torch.distributed as dist
 from .. import config as C
 from ..data.order import OrderSpec, apply_augment, unpack_aug
 from ..models import build_model
-from ..models.cifar_cnn import decay_mask
+from ..models.cifar_cnn import CifarCNN, decay_mask
+
+# evaluate()'s default on the hip_f32 backend at crop 24: "hip" (one launch of k_cnn_infer_f32) or
+# "batched" (the batch walk); set by the same-session A/B of tools/f32_infer_ab.py
+# (profiles/f32_infer_ab.txt: "hip" is faster on 10,000 images, with the same hit count)
+EVAL_IMPL_F32 = "hip"
 
 
 class EagerTrainer:
@@ -232,8 +237,49 @@ class EagerTrainer:
         if step is not None:
             self.global_step = int(step)
 
+    # --- inference / evaluation (hip_f32 backend: one launch of k_cnn_infer_f32) -----------------------
+    def _one_launch(self) -> bool:
+        """Whether the one-launch fp32 kernel serves this trainer: the CIFAR CNN on the fp32 HIP backend
+        at the 24x24 crop (the only crop the fused kernels serve)."""
+        return self.backend == "hip_f32" and self.crop == 24 and isinstance(self.model, CifarCNN)
+
     @torch.no_grad()
-    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0) -> float:
+    def infer(self, images_u8: torch.Tensor, labels: Optional[torch.Tensor] = None,
+              idx: Optional[torch.Tensor] = None, blocks: Optional[int] = None):
+        """Eval-mode forward of any uint8 [N,32,32,3] images in ONE launch of k_cnn_infer_f32
+        (ops/f32.py cnn_infer_f32): (logits fp32 [n,10], pred int32 [n], hits int32 [n] or None without
+        ``labels``), every product on the fp32 MFMA from the flat fp32 parameters as the last step left
+        them, at the centre crop.  Writes no training state."""
+        if not self._one_launch():
+            raise ValueError("infer: the one-launch fp32 kernel needs the cifar_cnn model on the hip_f32 "
+                             "backend at crop 24")
+        from ..ops.f32 import cnn_infer_f32
+        return cnn_infer_f32(images_u8, self.model.flat, labels, idx, blocks, self.model.relu_logits,
+                             (self.off, self.off))
+
+    def infer_logits(self, images_u8: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                     blocks: Optional[int] = None) -> torch.Tensor:
+        """Eval-mode logits fp32 [n,10] of uint8 images (see :meth:`infer`)."""
+        return self.infer(images_u8, None, idx, blocks)[0]
+
+    @torch.no_grad()
+    def evaluate(self, data: torch.Tensor, labels: torch.Tensor, max_batches: int = 0,
+                 impl: Optional[str] = None) -> float:
+        """Test accuracy over ``data`` (uint8 [N,32,32,3]).  ``impl="batched"``: batch by batch through
+        the model's forward; ``impl="hip"`` (hip_f32 backend, crop 24): the first ``max_batches * batch``
+        images (0: all) through k_cnn_infer_f32 in one launch, the hits summed on the device and read
+        back once.  Default: ``EVAL_IMPL_F32`` where the kernel serves the trainer, else "batched"."""
+        if impl is None:
+            impl = EVAL_IMPL_F32 if self._one_launch() else "batched"
+        if impl not in ("hip", "batched"):
+            raise ValueError(f"evaluate: impl must be 'hip' or 'batched', got {impl!r}")
+        if impl == "hip":
+            n = data.shape[0]
+            if max_batches:
+                n = min(n, max_batches * self.B)
+            if n == 0:
+                return 0.0
+            return int(self.infer(data[:n], labels[:n])[2].sum()) / n
         self.model.eval()
         n = data.shape[0]
         nb = math.ceil(n / self.B)

@@ -271,8 +271,8 @@ class _EagerAdapter:
             b.copy_(t.to(b.device))
         self.tr.global_step = int(step.item())
 
-    def evaluate(self, x, y, max_batches=0) -> float:
-        return self.tr.evaluate(x, y, max_batches)
+    def evaluate(self, x, y, max_batches=0, impl=None) -> float:
+        return self.tr.evaluate(x, y, max_batches, impl=impl)
 
     def sync(self):
         if self.tr.device.type == "cuda":

@@ -13,13 +13,17 @@ column matrix is ever written.  Other geometries (e.g. another crop) use ``f32_i
 the gather-form ``f32_col2im`` adjoint.  fc bias gradients: ``f32_colsum``.  ReLU, the TF-SAME max-pool and the loss
 are fp32 PyTorch ops (exact in fp32; no rounding choice to make).
 
+Inference and evaluation have a kernel of their own: ``cnn_infer_f32`` runs the whole eval-mode forward,
+uint8 pixels to fp32 logits, predictions and hit flags, in ONE launch of ``k_cnn_infer_f32``
+(csrc/kernels/f32_infer.hip) -- the same fp32 MFMA, no PyTorch op in between.
+
 Activations are NHWC and weights keep the TF layouts (HWIO / [in, out]), so the weights are
 views of the model's flat parameter buffer and the im2col column order (kh, kw, ci) is the row
 order of the HWIO weight viewed as [kh*kw*ci, co] -- no transposes anywhere.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -166,6 +170,44 @@ class _FlatViews(torch.autograd.Function):
 def flat_views(flat: torch.Tensor, specs) -> Dict[str, torch.Tensor]:
     from ..models.cifar_cnn import short
     return {short(s.name): v for s, v in zip(specs, _FlatViews.apply(flat, tuple(specs)))}
+
+
+_INFER_SCRATCH: Dict[tuple, torch.Tensor] = {}   # (device, workgroups) -> fp32 [workgroups, 16, 2304]
+
+
+@torch.no_grad()
+def cnn_infer_f32(images_u8: torch.Tensor, flat: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                  idx: Optional[torch.Tensor] = None, blocks: Optional[int] = None, relu_logits: bool = True,
+                  crop_offset=(4, 4)):
+    """Eval-mode forward of uint8 [N,32,32,3] images (on any device) in ONE launch of k_cnn_infer_f32
+    (csrc/kernels/f32_infer.hip), every product on the fp32 MFMA: (logits fp32 [n,10], pred int32 [n],
+    hits int32 [n] or None without ``labels``).  ``flat``: the model's flat fp32 parameter buffer on the
+    GPU (models/cifar_cnn.py PARAM_SPECS), read in place; ``idx``: rows of ``images_u8`` to run
+    (n = len(idx)), else all of them; ``labels``: one per row of ``images_u8``; ``blocks``: workgroups
+    of the persistent loop (None: one per CU); ``crop_offset``: top-left corner of the 24x24 crop."""
+    from ..models.cifar_cnn import PARAM_SPECS
+    ops = _ops()
+    dev = flat.device
+    if images_u8.dtype != torch.uint8 or tuple(images_u8.shape[1:]) != (32, 32, 3):
+        raise ValueError(f"cnn_infer_f32: images must be uint8 [N,32,32,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+    images_u8 = images_u8.to(dev).contiguous()
+    if idx is not None:
+        idx = idx.to(dev, torch.int32).reshape(-1).contiguous()
+    n = images_u8.shape[0] if idx is None else idx.numel()
+    if labels is not None:
+        labels = labels.to(dev, torch.int32).reshape(-1).contiguous()
+    logits = torch.empty(n, 10, dtype=torch.float32, device=dev)
+    pred = torch.empty(n, dtype=torch.int32, device=dev)
+    hits = None if labels is None else torch.empty(n, dtype=torch.int32, device=dev)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    grid = max(1, min(-(-n // 16), int(blocks) if blocks else max(1, cus)))
+    key = (dev, grid)
+    if key not in _INFER_SCRATCH:        # one [16][2304] slab of pooled activations per workgroup
+        _INFER_SCRATCH[key] = torch.empty(grid, 16, 2304, dtype=torch.float32, device=dev)
+    ops.f32_cnn_infer(images_u8, idx, labels, int(crop_offset[0]), int(crop_offset[1]), flat.detach(),
+                      [s.offset for s in PARAM_SPECS], bool(relu_logits), _INFER_SCRATCH[key], logits, pred, hits,
+                      int(blocks or 0))
+    return logits, pred, hits
 
 
 def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True) -> torch.Tensor:
