@@ -1,10 +1,11 @@
-// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip): the building blocks
+// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_pool.hip): the building blocks
 // of the fp32-accurate CNN path (ops/f32.py).  Functional ops (they allocate their outputs on the
 // caching allocator and launch on the current HIP stream, so they compose with autograd and are
 // capturable into HIP graphs); every launch is preceded by a full shape / dtype / layout check.
 #include <c10/core/DeviceGuard.h>
 
 #include <algorithm>
+#include <tuple>
 
 #include "../kernels/api_f32.h"
 #include "check.h"
@@ -130,6 +131,66 @@ Tensor f32_colsum(const Tensor& x) {
   return out;
 }
 
+// ReLU + TF-SAME 3x3/2 max-pool of a conv output (f32_pool.hip): y fp32 NHWC [B, H, H, 64], H = 24 or 12 ->
+// (p fp32 [B, H/2, H/2, 64] = pool(relu(y)), arg uint8 of the same shape = kh*3 + kw of the first maximum,
+// 255 where the window's maximum is <= 0).  blocks: workgroups of the grid-stride loop (0: default).
+void pool_geom(const Tensor& t, const char* n, int64_t h0, int64_t h1, int64_t blocks) {
+  TORCH_CHECK(t.dim() == 4 && t.size(0) >= 1 && t.size(0) <= (1 << 20) && (t.size(1) == h0 || t.size(1) == h1) &&
+                  t.size(2) == t.size(1) && t.size(3) == 64,
+              n, " must be [1 <= B <= 2^20, H, H, 64] with H = ", h0, " or ", h1, ", got ", t.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, n, " must be 16-byte aligned");
+  TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "blocks must be >= 0 (0: the default grid)");
+}
+
+std::tuple<Tensor, Tensor> f32_relu_pool_fwd(const Tensor& y, int64_t blocks) {
+  f32_in(y, "y", 4);
+  pool_geom(y, "y", 24, 12, blocks);
+  const int64_t B = y.size(0), H = y.size(1);
+  const c10::DeviceGuard g(y.device());
+  auto p = at::empty({B, H / 2, H / 2, 64}, y.options());
+  auto arg = at::empty({B, H / 2, H / 2, 64}, y.options().dtype(at::kByte));
+  CHECK_HIP(dmlc_f32_relu_pool_fwd(y.data_ptr<float>(), p.data_ptr<float>(), arg.data_ptr<uint8_t>(), (int)B, (int)H,
+                                   (int)blocks, stream_of(y)));
+  return {p, arg};
+}
+
+// Its backward and the ReLU's in one pass: dp fp32, arg uint8 [B, H/2, H/2, 64] -> dy fp32 [B, H, H, 64].
+Tensor f32_relu_pool_bwd(const Tensor& dp, const Tensor& arg, int64_t blocks) {
+  f32_in(dp, "dp", 4);
+  pool_geom(dp, "dp", 12, 6, blocks);
+  check(arg, "arg", at::kByte, dp.sizes().vec());
+  TORCH_CHECK(arg.device() == dp.device(), "f32_relu_pool_bwd: dp and arg on different devices");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(arg.data_ptr()) % 16 == 0, "arg must be 16-byte aligned");
+  const int64_t B = dp.size(0), H = 2 * dp.size(1);
+  const c10::DeviceGuard g(dp.device());
+  auto dy = at::empty({B, H, H, 64}, dp.options());
+  CHECK_HIP(dmlc_f32_relu_pool_bwd(dp.data_ptr<float>(), arg.data_ptr<uint8_t>(), dy.data_ptr<float>(), (int)B, (int)H,
+                                   (int)blocks, stream_of(dp)));
+  return dy;
+}
+
+// Softmax cross-entropy head (f32_pool.hip): logits fp32 [B, 10] (before the optional logit ReLU), labels int32
+// or int64 [B] -> (loss fp32 [] = mean cross-entropy, of relu(logits) with relu_logits; hits int32 [] = rows
+// whose first maximum is the label; dlogits fp32 [B, 10] = d loss / d logits).
+std::tuple<Tensor, Tensor, Tensor> f32_xent_head(const Tensor& logits, const Tensor& labels, bool relu_logits) {
+  f32_in(logits, "logits", 2);
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(B >= 1 && B <= (1 << 27) && logits.size(1) == 10, "logits must be [1 <= B <= 2^27, 10], got ",
+              logits.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 8 == 0, "logits must be 8-byte aligned");
+  const bool l64 = labels.scalar_type() == at::kLong;
+  check(labels, "labels", l64 ? at::kLong : at::kInt, {B});
+  TORCH_CHECK(labels.device() == logits.device(), "f32_xent_head: logits and labels on different devices");
+  const c10::DeviceGuard g(logits.device());
+  auto loss = at::empty({}, logits.options());
+  auto hits = at::empty({}, logits.options().dtype(at::kInt));
+  auto dl = at::empty({B, 10}, logits.options());
+  CHECK_HIP(dmlc_f32_xent_head(logits.data_ptr<float>(), labels.data_ptr(), l64 ? 1 : 0, dl.data_ptr<float>(),
+                               loss.data_ptr<float>(), hits.data_ptr<int>(), (int)B, relu_logits ? 1 : 0,
+                               stream_of(logits)));
+  return {loss, hits, dl};
+}
+
 // The whole eval-mode forward in true fp32, one launch (f32_infer.hip): image i is data[idx[i]] (idx None:
 // data[i], N = data rows); writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels,
 // one per data row).  flat: the model's fp32 parameter buffer, off: the element offsets of its ten TF-layout
@@ -216,6 +277,9 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
   m.def("f32_im2col(Tensor x, int kh, int kw, int pad) -> Tensor");
   m.def("f32_col2im(Tensor dcols, int B, int H, int W, int C, int kh, int kw, int pad) -> Tensor");
   m.def("f32_colsum(Tensor x) -> Tensor");
+  m.def("f32_relu_pool_fwd(Tensor y, int blocks=0) -> (Tensor, Tensor)");
+  m.def("f32_relu_pool_bwd(Tensor dp, Tensor arg, int blocks=0) -> Tensor");
+  m.def("f32_xent_head(Tensor logits, Tensor labels, bool relu_logits) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
@@ -224,5 +288,8 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_im2col", &f32_im2col);
   m.impl("f32_col2im", &f32_col2im);
   m.impl("f32_colsum", &f32_colsum);
+  m.impl("f32_relu_pool_fwd", &f32_relu_pool_fwd);
+  m.impl("f32_relu_pool_bwd", &f32_relu_pool_bwd);
+  m.impl("f32_xent_head", &f32_xent_head);
   m.impl("f32_cnn_infer", &f32_cnn_infer);
 }

@@ -55,4 +55,20 @@ typedef struct {
 hipError_t dmlc_f32_infer_grid(int N, int blocks, int* grid);
 hipError_t dmlc_f32_infer(const DmlcF32InferArgs* a, hipStream_t s);
 
+// csrc/kernels/f32_pool.hip: the ReLU + TF-SAME 3x3/2 max-pool of a conv stage and the loss head.
+// k_f32_relu_pool_fwd: y NHWC [B][H][H][64] (H = 24 or 12) -> p [B][H/2][H/2][64] = pool(relu(y)) and
+// arg (same shape, one byte each) = kh*3 + kw of the window's first maximum, 255 where it is <= 0.
+// blocks: workgroups of the grid-stride loop over the launch's units (0: the default cap).  Every
+// pointer 16-byte aligned.
+hipError_t dmlc_f32_relu_pool_fwd(const float* y, float* p, uint8_t* arg, int B, int H, int blocks, hipStream_t s);
+// k_f32_relu_pool_bwd: dp, arg [B][H/2][H/2][64] -> dy [B][H][H][64], the gradient at the conv output
+// (pool and ReLU backward; every element written, fixed summation order).
+hipError_t dmlc_f32_relu_pool_bwd(const float* dp, const uint8_t* arg, float* dy, int B, int H, int blocks,
+                                  hipStream_t s);
+// k_f32_xent_head: logits [B][10] (before the optional logit ReLU), labels [B] (int32, or int64 with
+// labels64) -> *loss = mean softmax cross-entropy (of relu(logits) with relu_logits), *hits = rows whose
+// first maximum is the label, dlogits [B][10] = d loss / d logits.  One workgroup, deterministic.
+hipError_t dmlc_f32_xent_head(const float* logits, const void* labels, int labels64, float* dlogits, float* loss,
+                              int* hits, int B, int relu_logits, hipStream_t s);
+
 }  // extern "C"

@@ -1,8 +1,8 @@
 """Eager (PyTorch-op) training engine.
 
 Used for (a) the CPU "plumbing" configuration (BASELINE config 1), (b) the fp32-accurate GPU mode
-(``backend='hip_f32'``: the model's matmuls/convs on the fp32 HIP kernels of ops/f32.py, driven
-step by step from here, optionally captured into one HIP graph), (c) the framework-default
+(``backend='hip_f32'``: the model's matmuls/convs, ReLU + pool and loss head on the fp32 HIP kernels
+of ops/f32.py, driven step by step from here, optionally captured into one HIP graph), (c) the framework-default
 comparison line of the benchmark, and (d) the numerics oracle for the fused engines.  Semantics follow the reference training step
 (/root/reference/cifar10cnn.py:159-164, :230): sparse softmax cross-entropy (mean), plain SGD,
 staircase LR decay, global_step++; ``momentum`` / ``weight_decay`` (both 0 by default) turn the
@@ -35,7 +35,7 @@ class EagerTrainer:
                  decay_steps: float = C.NUM_GENS_TO_WAIT, staircase: bool = True, relu_logits: bool = True,
                  crop: int = C.CROP_HEIGHT, seed: int = 0, flat_params: Optional[torch.Tensor] = None,
                  augment: bool = False, graph: bool = False, warmup_steps: int = 0, backend: str = "torch",
-                 momentum: float = 0.0, weight_decay: float = 0.0):
+                 momentum: float = 0.0, weight_decay: float = 0.0, fused: bool = True):
         self.device = torch.device(device)
         if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
             raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
@@ -48,8 +48,10 @@ class EagerTrainer:
         if backend == "hip_f32" and (self.device.type != "cuda" or dtype != "fp32"):
             raise ValueError("the hip_f32 backend is the fp32 GPU path (device cuda, dtype fp32)")
         self.backend = backend
+        # fused (hip_f32 backend only): ReLU + pool and the loss head on their HIP kernels (ops/f32.py
+        # relu_pool / xent_head); False keeps them PyTorch ops -- the reference path of tools/f32_step_ab.py
         self.model = build_model(model, seed=seed, relu_logits=relu_logits, flat=flat_params,
-                                 backend=backend).to(self.device)
+                                 backend=backend, fused=fused).to(self.device)
         self.B = int(batch_size)
         self.data = data.to(self.device)
         self.labels = labels.to(self.device).long()
@@ -155,10 +157,14 @@ class EagerTrainer:
 
     def _fwd_bwd_sgd(self, x, y, lr):
         """One training step's device work; ``lr`` is a float or a 0-d device tensor."""
-        use_amp = self.dtype == "bf16" and self.device.type == "cuda"
-        with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=use_amp):
-            logits = self.model(x)
-        loss = torch.nn.functional.cross_entropy(logits.float(), y)
+        hip_head = self.backend == "hip_f32" and self.model.fused      # loss + hit count: k_f32_xent_head
+        if hip_head:
+            loss, hits = self.model.loss_and_hits(x, y)
+        else:
+            use_amp = self.dtype == "bf16" and self.device.type == "cuda"
+            with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=use_amp):
+                logits = self.model(x)
+            loss = torch.nn.functional.cross_entropy(logits.float(), y)
         loss.backward()
         self._allreduce_grads()
         with torch.no_grad():
@@ -172,6 +178,8 @@ class EagerTrainer:
                         p.add_(p.grad, alpha=-lr)
         if hasattr(self.model, "after_step"):
             self.model.after_step()
+        if hip_head:
+            return loss.detach(), hits / float(y.numel())
         return loss.detach(), (logits.detach().argmax(1) == y).float().mean()
 
     def step(self):

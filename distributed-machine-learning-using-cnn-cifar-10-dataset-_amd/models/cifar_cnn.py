@@ -163,12 +163,14 @@ class CifarCNN(nn.Module):
     specs = PARAM_SPECS
 
     def __init__(self, flat: torch.Tensor | None = None, relu_logits: bool = True, seed: int = 0,
-                 backend: str = "torch"):
+                 backend: str = "torch", fused: bool = True):
         super().__init__()
         if backend not in ("torch", "hip_f32"):
             raise ValueError(f"unknown CNN backend {backend!r}")
-        # 'hip_f32': every matmul/conv on the fp32 HIP kernels (ops/f32.py) -- reference precision
+        # 'hip_f32': every matmul/conv on the fp32 HIP kernels (ops/f32.py) -- reference precision;
+        # fused (that backend only): ReLU + pool and the loss head on their HIP kernels too, else PyTorch ops
         self.backend = backend
+        self.fused = bool(fused)
         if flat is None:
             g = torch.Generator().manual_seed(seed)
             flat = init_flat_params(g)
@@ -181,8 +183,18 @@ class CifarCNN(nn.Module):
     def forward(self, images_nhwc: torch.Tensor) -> torch.Tensor:
         if self.backend == "hip_f32":
             from ..ops.f32 import cnn_forward_f32, flat_views
-            return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits)
+            return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits, self.fused)
         return cnn_forward(images_nhwc, self.params(), self.relu_logits)
+
+    def loss_and_hits(self, images_nhwc: torch.Tensor, labels: torch.Tensor):
+        """hip_f32 backend: (mean cross-entropy, count of rows whose first maximum is the label) of a batch,
+        the loss head on k_f32_xent_head (ops/f32.py xent_head) -- what ``cifar_loss`` and ``batch_accuracy``
+        * B give on this model's logits."""
+        if self.backend != "hip_f32":
+            raise ValueError("loss_and_hits is the hip_f32 backend's loss head")
+        from ..ops.f32 import cnn_forward_f32, flat_views, xent_head
+        raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused)
+        return xent_head(raw, labels.view(-1), self.relu_logits)
 
     def named_tf_variables(self) -> Dict[str, torch.Tensor]:
         return {s.name: self.flat.detach()[s.offset:s.offset + s.numel].view(s.shape) for s in self.specs}

@@ -10,8 +10,15 @@ fp32 operands, deterministic split-K).  The two convolutions are implicit GEMMs
 forward = im2col(x) W, weight + bias gradient = im2col(x)^T dY with a ones column (its output row
 is the bias gradient), data gradient = im2col(dY) against the flipped, transposed weight -- no
 column matrix is ever written.  Other geometries (e.g. another crop) use ``f32_im2col`` + GEMM with
-the gather-form ``f32_col2im`` adjoint.  fc bias gradients: ``f32_colsum``.  ReLU, the TF-SAME max-pool and the loss
-are fp32 PyTorch ops (exact in fp32; no rounding choice to make).
+the gather-form ``f32_col2im`` adjoint.  fc bias gradients: ``f32_colsum``.
+
+The rest of the step is HIP as well (csrc/kernels/f32_pool.hip): ``relu_pool`` is the ReLU + TF-SAME 3x3/2
+max-pool of a conv stage in one kernel each way -- the forward also writes a one-byte argmax per pooled
+element (255 = masked by the ReLU), the only thing the backward keeps, and the backward writes the gradient
+at the conv output in one gather pass (no zero-fill, no atomics) -- and ``xent_head`` is the softmax
+cross-entropy, the batch's hit count and dlogits in one launch.  The forward is bit-identical to the PyTorch
+ops; the backward differs by the order of at most four addends per element.  ``cnn_forward_f32(fused=False)``
+keeps ``torch.relu`` + ``max_pool2d`` as the reference path; the two small fc ReLUs are PyTorch ops either way.
 
 Inference and evaluation have a kernel of their own: ``cnn_infer_f32`` runs the whole eval-mode forward,
 uint8 pixels to fp32 logits, predictions and hit flags, in ONE launch of ``k_cnn_infer_f32``
@@ -141,6 +148,56 @@ def _pool_nhwc(x: torch.Tensor) -> torch.Tensor:
     return y if y.is_contiguous() else y.contiguous()
 
 
+_FUSED_POOL = {24, 12}                   # H of the [B,H,H,64] conv outputs k_f32_relu_pool_* serve
+
+
+class _ReluPool(torch.autograd.Function):
+    """pool(relu(y)) of a conv output in one kernel each way (csrc/kernels/f32_pool.hip).  Saves the
+    one-byte argmax only: the backward needs neither y nor relu(y)."""
+
+    @staticmethod
+    def forward(ctx, y, blocks):
+        p, arg = _ops().f32_relu_pool_fwd(y.contiguous(), blocks)
+        ctx.save_for_backward(arg)
+        ctx.blocks = blocks
+        return p
+
+    @staticmethod
+    def backward(ctx, gp):
+        (arg,) = ctx.saved_tensors
+        return _ops().f32_relu_pool_bwd(gp.contiguous(), arg, ctx.blocks), None
+
+
+def relu_pool(y: torch.Tensor, blocks: int = 0) -> torch.Tensor:
+    """TF-SAME 3x3/2 max-pool of relu(y), y fp32 NHWC [B,H,H,64] with H = 24 or 12; bit-identical to
+    ``_pool_nhwc(torch.relu(y))``.  ``blocks``: workgroups of the kernels' grid-stride loops (0: default)."""
+    return _ReluPool.apply(y, int(blocks))
+
+
+class _XentHead(torch.autograd.Function):
+    """(mean softmax cross-entropy, hit count) of the fc3 output in one launch of k_f32_xent_head, which
+    also leaves d loss / d logits for the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, relu_logits):
+        loss, hits, dlogits = _ops().f32_xent_head(logits.contiguous(), labels.contiguous(), relu_logits)
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(hits)
+        return loss, hits
+
+    @staticmethod
+    def backward(ctx, gloss, _ghits):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * gloss, None, None
+
+
+def xent_head(logits: torch.Tensor, labels: torch.Tensor, relu_logits: bool):
+    """``logits``: the fc3 output fp32 [B,10] BEFORE the optional logit ReLU; ``labels``: int32 or int64 [B]
+    in [0, 10).  Returns (loss fp32 [] = mean cross-entropy of relu(logits) if ``relu_logits`` else of
+    logits, hits int32 [] = rows whose first maximum is the label)."""
+    return _XentHead.apply(logits, labels, bool(relu_logits))
+
+
 class _FlatViews(torch.autograd.Function):
     """The per-variable tensors of a flat parameter buffer whose backward builds the flat gradient
     in ONE concatenation (autograd through plain views of a leaf would zero-fill a full-size
@@ -210,12 +267,22 @@ def cnn_infer_f32(images_u8: torch.Tensor, flat: torch.Tensor, labels: Optional[
     return logits, pred, hits
 
 
-def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True) -> torch.Tensor:
-    """The reference CNN (models/cifar_cnn.py:cnn_forward semantics) on the fp32 HIP kernels."""
+def _conv_stage(x, w, b, fused: bool):
+    y = conv_same(x, w, b)
+    if fused and y.shape[1] == y.shape[2] and y.shape[1] in _FUSED_POOL and y.shape[3] == 64:
+        return relu_pool(y)
+    return _pool_nhwc(torch.relu(y))
+
+
+def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True,
+                    fused: bool = True) -> torch.Tensor:
+    """The reference CNN (models/cifar_cnn.py:cnn_forward semantics) on the fp32 HIP kernels.  ``fused``:
+    ReLU + pool of the conv stages through ``relu_pool`` where the geometry is one of its two ([B,24,24,64],
+    [B,12,12,64]); otherwise, and with ``fused=False``, the PyTorch ops (same logits bit for bit)."""
     x = images_nhwc.float().contiguous()
-    x = _pool_nhwc(torch.relu(conv_same(x, p["conv1_kernel"], p["conv1_bias"])))
-    x = _pool_nhwc(torch.relu(conv_same(x, p["conv2_kernel"], p["conv2_bias"])))
-    x = x.reshape(x.shape[0], -1)                                  # NHWC flatten (cifar10cnn.py:126)
+    x = _conv_stage(x, p["conv1_kernel"], p["conv1_bias"], fused)
+    x = _conv_stage(x, p["conv2_kernel"], p["conv2_bias"], fused)
+    x = x.reshape(x.shape[0], -1)                               # NHWC flatten (cifar10cnn.py:126)
     x = torch.relu(linear(x, p["full_weight_1"], p["full_bias_1"]))
     x = torch.relu(linear(x, p["full_weight_2"], p["full_bias_2"]))
     x = linear(x, p["full_weight_3"], p["full_bias_3"])
