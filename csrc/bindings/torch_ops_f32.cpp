@@ -1,4 +1,4 @@
-// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_pool.hip): the building blocks
+// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_conv.hip, f32_pool.hip): the building blocks
 // of the fp32-accurate CNN path (ops/f32.py).  Functional ops (they allocate their outputs on the
 // caching allocator and launch on the current HIP stream, so they compose with autograd and are
 // capturable into HIP graphs); every launch is preceded by a full shape / dtype / layout check.
@@ -92,6 +92,36 @@ Tensor f32_conv_gemm(const Tensor& x, const Tensor& w, const c10::optional<Tenso
                           splits > 1 ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, 0, (int)N, ta, false,
                           false, splits, kcs, geom, stream_of(x)));
   return out;
+}
+
+// Direct conv2 (f32_conv.hip): x fp32 NHWC [B, 12, 12, 64], w the HWIO weight [5, 5, 64, 64] (or its
+// [1600, 64] view) -> [B, 12, 12, 64].  dgrad = false: conv(x, w) + bias; dgrad = true: x is dY and the result
+// dX, with w read in place as the flipped, transposed weight (no bias).  blocks: workgroups (0: one per CU).
+Tensor f32_conv2_direct(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, bool dgrad,
+                        int64_t blocks) {
+  f32_in(x, "x", 4);
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= (1 << 20) && x.size(1) == 12 && x.size(2) == 12 && x.size(3) == 64,
+              "f32_conv2_direct: x must be [1 <= B <= 2^20, 12, 12, 64], got ", x.sizes());
+  f32_in(w, "w", w.dim() == 2 ? 2 : 4);
+  TORCH_CHECK(w.sizes() == at::IntArrayRef({5, 5, 64, 64}) || w.sizes() == at::IntArrayRef({1600, 64}),
+              "f32_conv2_direct: w must be [5, 5, 64, 64] or [1600, 64], got ", w.sizes());
+  TORCH_CHECK(w.device() == x.device(), "f32_conv2_direct: x and w on different devices");
+  TORCH_CHECK(blocks >= 0 && blocks < (1ll << 31), "f32_conv2_direct: blocks must be >= 0 (0: one workgroup per CU)");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(!dgrad, "f32_conv2_direct: the data gradient takes no bias");
+    check(*bias, "bias", at::kFloat, {64});
+    TORCH_CHECK(bias->device() == x.device(), "f32_conv2_direct: x and bias on different devices");
+    bp = bias->data_ptr<float>();
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(bp) % 16 == 0,
+              "f32_conv2_direct: x, w and bias must be 16-byte aligned");
+  const c10::DeviceGuard g(x.device());
+  auto y = at::empty({x.size(0), 12, 12, 64}, x.options());
+  CHECK_HIP(dmlc_f32_conv2(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)x.size(0),
+                           dgrad ? 1 : 0, (int)blocks, stream_of(x)));
+  return y;
 }
 
 Tensor f32_im2col(const Tensor& x, int64_t kh, int64_t kw, int64_t pad) {
@@ -274,6 +304,7 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
         "int blocks=0) -> ()");
   m.def("f32_gemm(Tensor a, Tensor b, Tensor? bias, bool ta, bool tb, bool relu) -> Tensor");
   m.def("f32_conv_gemm(Tensor x, Tensor w, Tensor? bias, bool ta, bool ones) -> Tensor");
+  m.def("f32_conv2_direct(Tensor x, Tensor w, Tensor? bias, bool dgrad, int blocks=0) -> Tensor");
   m.def("f32_im2col(Tensor x, int kh, int kw, int pad) -> Tensor");
   m.def("f32_col2im(Tensor dcols, int B, int H, int W, int C, int kh, int kw, int pad) -> Tensor");
   m.def("f32_colsum(Tensor x) -> Tensor");
@@ -285,6 +316,7 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
 TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_gemm", &f32_gemm);
   m.impl("f32_conv_gemm", &f32_conv_gemm);
+  m.impl("f32_conv2_direct", &f32_conv2_direct);
   m.impl("f32_im2col", &f32_im2col);
   m.impl("f32_col2im", &f32_col2im);
   m.impl("f32_colsum", &f32_colsum);

@@ -55,6 +55,14 @@ typedef struct {
 hipError_t dmlc_f32_infer_grid(int N, int blocks, int* grid);
 hipError_t dmlc_f32_infer(const DmlcF32InferArgs* a, hipStream_t s);
 
+// k_f32_conv2 (csrc/kernels/f32_conv.hip): the stride-1 TF-SAME 5x5 convolution of x NHWC [B][12][12][64]
+// with 64 output channels, direct (the image in LDS, the weights streamed as MFMA fragments), no ReLU.
+// w: the HWIO weight [5][5][64][64].  dgrad = 0: y = conv(x, w) + bias (bias [64] or null).  dgrad = 1: x is
+// dY and y = dX, the data gradient, with w read in place as W[4-kh][4-kw][ci][co] (bias must be null).
+// blocks: workgroups of the persistent loop over images, 0 = one per CU.  Every pointer 16-byte aligned.
+hipError_t dmlc_f32_conv2(const float* x, const float* w, const float* bias, float* y, int B, int dgrad, int blocks,
+                          hipStream_t s);
+
 // csrc/kernels/f32_pool.hip: the ReLU + TF-SAME 3x3/2 max-pool of a conv stage and the loss head.
 // k_f32_relu_pool_fwd: y NHWC [B][H][H][64] (H = 24 or 12) -> p [B][H/2][H/2][64] = pool(relu(y)) and
 // arg (same shape, one byte each) = kh*3 + kw of the window's first maximum, 255 where it is <= 0.

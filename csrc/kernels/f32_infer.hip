@@ -67,6 +67,7 @@
 //   band stores    windows within every lane group -- 4 cycles.
 #include "common.h"
 #include "api_f32.h"
+#include "f32_conv_core.h"   // mfma_f32, lds4, p1_off, p1_tile, out_tile
 
 namespace dmlc {
 
@@ -86,8 +87,6 @@ constexpr int FI_LDS = FI_CONV_LDS > FI_FC_LDS ? FI_CONV_LDS : FI_FC_LDS;
 static_assert(FI_LDS <= 160 * 1024 && FI_X % 16 == 0 && FI_BAND % 16 == 0 && FI_P1 % 16 == 0 && FI_H1 % 16 == 0 &&
                   FI_H2 % 16 == 0 && 144 * FI_BLD <= FI_BPIX * FI_BLD, "f32_infer LDS map");
 
-DEV f32x4 mfma_f32(float a, float b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-DEV f32x4 lds4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 DEV f32x4 max4(const f32x4& a, const f32x4& b) {
   f32x4 m = {fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])};
   return m;
@@ -98,11 +97,6 @@ DEV f32x4 bias_relu(const f32x4& acc, const float* bias) {
   f32x4 v = {fmaxf(acc[0] + b.x, 0.f), fmaxf(acc[1] + b.y, 0.f), fmaxf(acc[2] + b.z, 0.f), fmaxf(acc[3] + b.w, 0.f)};
   return v;
 }
-// float offset in p1 of channel chunk c (4 floats) of padded pixel (py, px)
-DEV int p1_off(int py, int px, int c) { return (py * 16 + px) * 64 + ((c ^ ((px & 3) | ((py & 3) << 2))) << 2); }
-// float offset of conv2 pixel tile t (a 4x4 block of the 12x12 output) in p1 / its first output pixel
-constexpr int p1_tile(int t) { return ((t / 3) * 4 * 16 + (t % 3) * 4) * 64; }
-constexpr int out_tile(int t) { return (t / 3) * 4 * 12 + (t % 3) * 4; }
 
 // conv1 of band b (conv rows 8b .. 8b + 8, clipped at 23) -> band [local pixel][64], bias + ReLU applied.
 DEV void conv1_band(const float* W1s, const float* xs, float* band, const float* b1, int b, int w, int q, int r) {

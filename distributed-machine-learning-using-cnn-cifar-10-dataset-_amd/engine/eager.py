@@ -35,7 +35,8 @@ class EagerTrainer:
                  decay_steps: float = C.NUM_GENS_TO_WAIT, staircase: bool = True, relu_logits: bool = True,
                  crop: int = C.CROP_HEIGHT, seed: int = 0, flat_params: Optional[torch.Tensor] = None,
                  augment: bool = False, graph: bool = False, warmup_steps: int = 0, backend: str = "torch",
-                 momentum: float = 0.0, weight_decay: float = 0.0, fused: bool = True):
+                 momentum: float = 0.0, weight_decay: float = 0.0, fused: bool = True,
+                 conv2_impl: Optional[str] = None):
         self.device = torch.device(device)
         if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
             raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
@@ -49,9 +50,11 @@ class EagerTrainer:
             raise ValueError("the hip_f32 backend is the fp32 GPU path (device cuda, dtype fp32)")
         self.backend = backend
         # fused (hip_f32 backend only): ReLU + pool and the loss head on their HIP kernels (ops/f32.py
-        # relu_pool / xent_head); False keeps them PyTorch ops -- the reference path of tools/f32_step_ab.py
+        # relu_pool / xent_head); False keeps them PyTorch ops -- the reference path of tools/f32_step_ab.py.
+        # conv2_impl (same backend): conv2's forward / data-gradient kernel, "direct" | "gemm" | None = the default
+        # ops/f32.py CONV2_IMPL_F32, set by the same-session A/B of tools/f32_conv_ab.py
         self.model = build_model(model, seed=seed, relu_logits=relu_logits, flat=flat_params,
-                                 backend=backend, fused=fused).to(self.device)
+                                 backend=backend, fused=fused, conv2_impl=conv2_impl).to(self.device)
         self.B = int(batch_size)
         self.data = data.to(self.device)
         self.labels = labels.to(self.device).long()

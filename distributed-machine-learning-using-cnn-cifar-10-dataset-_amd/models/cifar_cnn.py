@@ -163,7 +163,7 @@ class CifarCNN(nn.Module):
     specs = PARAM_SPECS
 
     def __init__(self, flat: torch.Tensor | None = None, relu_logits: bool = True, seed: int = 0,
-                 backend: str = "torch", fused: bool = True):
+                 backend: str = "torch", fused: bool = True, conv2_impl: str | None = None):
         super().__init__()
         if backend not in ("torch", "hip_f32"):
             raise ValueError(f"unknown CNN backend {backend!r}")
@@ -171,6 +171,11 @@ class CifarCNN(nn.Module):
         # fused (that backend only): ReLU + pool and the loss head on their HIP kernels too, else PyTorch ops
         self.backend = backend
         self.fused = bool(fused)
+        # conv2_impl (that backend only): conv2's forward / data-gradient kernel, "direct" | "gemm" | None
+        # (ops/f32.py CONV2_IMPL_F32); independent of fused
+        if conv2_impl not in (None, "direct", "gemm"):
+            raise ValueError(f"unknown conv2_impl {conv2_impl!r}")
+        self.conv2_impl = conv2_impl
         if flat is None:
             g = torch.Generator().manual_seed(seed)
             flat = init_flat_params(g)
@@ -183,7 +188,8 @@ class CifarCNN(nn.Module):
     def forward(self, images_nhwc: torch.Tensor) -> torch.Tensor:
         if self.backend == "hip_f32":
             from ..ops.f32 import cnn_forward_f32, flat_views
-            return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits, self.fused)
+            return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits, self.fused,
+                                   self.conv2_impl)
         return cnn_forward(images_nhwc, self.params(), self.relu_logits)
 
     def loss_and_hits(self, images_nhwc: torch.Tensor, labels: torch.Tensor):
@@ -193,7 +199,7 @@ class CifarCNN(nn.Module):
         if self.backend != "hip_f32":
             raise ValueError("loss_and_hits is the hip_f32 backend's loss head")
         from ..ops.f32 import cnn_forward_f32, flat_views, xent_head
-        raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused)
+        raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused, self.conv2_impl)
         return xent_head(raw, labels.view(-1), self.relu_logits)
 
     def named_tf_variables(self) -> Dict[str, torch.Tensor]:

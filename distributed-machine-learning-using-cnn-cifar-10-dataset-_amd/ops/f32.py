@@ -6,7 +6,9 @@ this module is the reference-precision alternative on the same kind of native co
 matrix product of the step -- conv forward, conv weight/data gradients, the three fc layers and
 their gradients -- runs on ``torch.ops.dmlc.f32_gemm`` (fp32 MFMA ``v_mfma_f32_16x16x4_f32``, true
 fp32 operands, deterministic split-K).  The two convolutions are implicit GEMMs
-(``f32_conv_gemm``: the tile loader gathers the im2col matrix straight from the NHWC activation):
+(``f32_conv_gemm``: the tile loader gathers the im2col matrix straight from the NHWC activation;
+conv2's forward and data gradient also have a direct kernel, ``f32_conv2_direct`` -- ``conv_same(impl=)``,
+``CONV2_IMPL_F32``):
 forward = im2col(x) W, weight + bias gradient = im2col(x)^T dY with a ones column (its output row
 is the bias gradient), data gradient = im2col(dY) against the flipped, transposed weight -- no
 column matrix is ever written.  Other geometries (e.g. another crop) use ``f32_im2col`` + GEMM with
@@ -98,6 +100,34 @@ class _ConvImplicit(torch.autograd.Function):
         return gx, gw, gb
 
 
+# conv2's forward and data gradient on the fp32 step: "direct" (k_f32_conv2, csrc/kernels/f32_conv.hip) or
+# "gemm" (the implicit GEMM of f32_gemm.hip with a flipped, transposed weight copy per backward); set by the
+# same-session A/B of tools/f32_conv_ab.py: "direct" only if it wins at B = 256 by more than the larger spread
+# of the two paths (profiles/f32_conv_ab.txt: 0.769 ms/step direct against 0.922 ms gemm, spreads 0.047 / 0.043)
+CONV2_IMPL_F32 = "direct"
+
+
+class _ConvDirect(torch.autograd.Function):
+    """conv2 ([B,12,12,64] -> 64 channels, 5x5 TF-'SAME') on k_f32_conv2: the image in LDS, the weights
+    streamed as MFMA fragments; the data gradient reads the same HWIO weight in place (no flipped or
+    transposed copy).  The weight + bias gradient stays the implicit GEMM im2col(x)^T dY."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.save_for_backward(x, w)
+        return _ops().f32_conv2_direct(x, w, b.contiguous(), False)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        ops = _ops()
+        gy = gy.contiguous()
+        gwb = ops.f32_conv_gemm(x, gy.view(-1, 64), None, True, True)            # [1601, 64]
+        gx = ops.f32_conv2_direct(gy, w, None, True) if ctx.needs_input_grad[0] else None
+        return gx, gwb[:1600].view(5, 5, 64, 64), gwb[1600]
+
+
 class _ConvSame(torch.autograd.Function):
     """Stride-1 TF-'SAME' KxK convolution, x NHWC [B,H,W,C], w HWIO [K,K,C,CO] -> NHWC (explicit
     im2col; geometries without an implicit kernel)."""
@@ -132,7 +162,14 @@ def linear(x, w, b):
     return _Linear.apply(x, w, b)
 
 
-def conv_same(x, w, b, implicit: bool = True):
+def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None):
+    """``impl``: "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernel of the [B,12,12,64] -> 64 geometry
+    (conv2); every other geometry takes the implicit / explicit GEMM path whatever ``impl`` says."""
+    if impl not in (None, "direct", "gemm"):
+        raise ValueError(f"conv_same: impl must be 'direct', 'gemm' or None, got {impl!r}")
+    if (impl or CONV2_IMPL_F32) == "direct" and (implicit or impl) and tuple(x.shape[1:]) == (12, 12, 64) \
+            and tuple(w.shape) == (5, 5, 64, 64):
+        return _ConvDirect.apply(x, w, b)
     if implicit and w.shape[0] == 5 and w.shape[1] == 5 and (x.shape[1], x.shape[3]) in _IMPLICIT \
             and x.shape[1] == x.shape[2]:
         return _ConvImplicit.apply(x, w, b)
@@ -267,21 +304,22 @@ def cnn_infer_f32(images_u8: torch.Tensor, flat: torch.Tensor, labels: Optional[
     return logits, pred, hits
 
 
-def _conv_stage(x, w, b, fused: bool):
-    y = conv_same(x, w, b)
+def _conv_stage(x, w, b, fused: bool, impl: Optional[str] = None):
+    y = conv_same(x, w, b, impl=impl)
     if fused and y.shape[1] == y.shape[2] and y.shape[1] in _FUSED_POOL and y.shape[3] == 64:
         return relu_pool(y)
     return _pool_nhwc(torch.relu(y))
 
 
 def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True,
-                    fused: bool = True) -> torch.Tensor:
+                    fused: bool = True, conv2_impl: Optional[str] = None) -> torch.Tensor:
     """The reference CNN (models/cifar_cnn.py:cnn_forward semantics) on the fp32 HIP kernels.  ``fused``:
     ReLU + pool of the conv stages through ``relu_pool`` where the geometry is one of its two ([B,24,24,64],
-    [B,12,12,64]); otherwise, and with ``fused=False``, the PyTorch ops (same logits bit for bit)."""
+    [B,12,12,64]); otherwise, and with ``fused=False``, the PyTorch ops (same logits bit for bit).
+    ``conv2_impl``: the second stage's conv kernel, ``conv_same``'s ``impl`` (independent of ``fused``)."""
     x = images_nhwc.float().contiguous()
     x = _conv_stage(x, p["conv1_kernel"], p["conv1_bias"], fused)
-    x = _conv_stage(x, p["conv2_kernel"], p["conv2_bias"], fused)
+    x = _conv_stage(x, p["conv2_kernel"], p["conv2_bias"], fused, conv2_impl)
     x = x.reshape(x.shape[0], -1)                               # NHWC flatten (cifar10cnn.py:126)
     x = torch.relu(linear(x, p["full_weight_1"], p["full_bias_1"]))
     x = torch.relu(linear(x, p["full_weight_2"], p["full_bias_2"]))
