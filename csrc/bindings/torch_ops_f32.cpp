@@ -124,6 +124,30 @@ Tensor f32_conv2_direct(const Tensor& x, const Tensor& w, const c10::optional<Te
   return y;
 }
 
+// Direct conv2 weight + bias gradient (f32_conv.hip k_f32_conv2_wgrad): x, dy fp32 NHWC [B, 12, 12, 64] ->
+// [1601, 64], the layout of f32_conv_gemm(x, dy, None, True, True).  groups: image groups = partial sums per
+// element (0: CUs / 4, always clamped to B); the partials live in a workspace of this call.
+Tensor f32_conv2_wgrad(const Tensor& x, const Tensor& dy, int64_t groups) {
+  f32_in(x, "x", 4);
+  f32_in(dy, "dy", 4);
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= (1 << 20) && x.size(1) == 12 && x.size(2) == 12 && x.size(3) == 64,
+              "f32_conv2_wgrad: x must be [1 <= B <= 2^20, 12, 12, 64], got ", x.sizes());
+  TORCH_CHECK(dy.sizes() == x.sizes(), "f32_conv2_wgrad: dy must have x's shape ", x.sizes(), ", got ", dy.sizes());
+  TORCH_CHECK(dy.device() == x.device(), "f32_conv2_wgrad: x and dy on different devices");
+  TORCH_CHECK(groups >= 0 && groups < (1ll << 31), "f32_conv2_wgrad: groups must be >= 0 (0: CUs / 4)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0,
+              "f32_conv2_wgrad: x and dy must be 16-byte aligned");
+  const c10::DeviceGuard g(x.device());
+  int G = 0;
+  size_t n = 0;
+  CHECK_HIP(dmlc_f32_conv2_wgrad_plan((int)x.size(0), (int)groups, &G, &n));
+  auto ws = at::empty({(int64_t)n}, x.options());
+  auto out = at::empty({1601, 64}, x.options());
+  CHECK_HIP(dmlc_f32_conv2_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), out.data_ptr<float>(), ws.data_ptr<float>(),
+                                 (int)x.size(0), G, stream_of(x)));
+  return out;
+}
+
 Tensor f32_im2col(const Tensor& x, int64_t kh, int64_t kw, int64_t pad) {
   f32_in(x, "x", 4);
   TORCH_CHECK(kh > 0 && kw > 0 && pad >= 0 && pad < kh && pad < kw, "f32_im2col: bad kernel/pad");
@@ -305,6 +329,7 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
   m.def("f32_gemm(Tensor a, Tensor b, Tensor? bias, bool ta, bool tb, bool relu) -> Tensor");
   m.def("f32_conv_gemm(Tensor x, Tensor w, Tensor? bias, bool ta, bool ones) -> Tensor");
   m.def("f32_conv2_direct(Tensor x, Tensor w, Tensor? bias, bool dgrad, int blocks=0) -> Tensor");
+  m.def("f32_conv2_wgrad(Tensor x, Tensor dy, int groups=0) -> Tensor");
   m.def("f32_im2col(Tensor x, int kh, int kw, int pad) -> Tensor");
   m.def("f32_col2im(Tensor dcols, int B, int H, int W, int C, int kh, int kw, int pad) -> Tensor");
   m.def("f32_colsum(Tensor x) -> Tensor");
@@ -317,6 +342,7 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_gemm", &f32_gemm);
   m.impl("f32_conv_gemm", &f32_conv_gemm);
   m.impl("f32_conv2_direct", &f32_conv2_direct);
+  m.impl("f32_conv2_wgrad", &f32_conv2_wgrad);
   m.impl("f32_im2col", &f32_im2col);
   m.impl("f32_col2im", &f32_col2im);
   m.impl("f32_colsum", &f32_colsum);

@@ -63,6 +63,16 @@ hipError_t dmlc_f32_infer(const DmlcF32InferArgs* a, hipStream_t s);
 hipError_t dmlc_f32_conv2(const float* x, const float* w, const float* bias, float* y, int B, int dgrad, int blocks,
                           hipStream_t s);
 
+// k_f32_conv2_wgrad + k_f32_wgrad_reduce (csrc/kernels/f32_conv.hip): conv2's weight and bias gradient, direct.
+// x, dy fp32 NHWC [B][12][12][64] -> out [1601][64]: row (kh*5 + kw)*64 + ci = dW[kh][kw][ci][:], row 1600 = db
+// (the layout of dmlc_f32_gemm's conv = 2 weight gradient with the ones column).  groups: image groups =
+// partial sums per output element, 0 = CUs / 4 (one workgroup per CU), clamped to B; the result is
+// bit-reproducible for a fixed (B, groups).  ws: the partials, written and read by this call only; _plan
+// returns the group count G used and the floats ws must hold.  Every pointer 16-byte aligned.
+hipError_t dmlc_f32_conv2_wgrad_plan(int B, int groups, int* G, size_t* ws_floats);
+hipError_t dmlc_f32_conv2_wgrad(const float* x, const float* dy, float* out, float* ws, int B, int groups,
+                                hipStream_t s);
+
 // csrc/kernels/f32_pool.hip: the ReLU + TF-SAME 3x3/2 max-pool of a conv stage and the loss head.
 // k_f32_relu_pool_fwd: y NHWC [B][H][H][64] (H = 24 or 12) -> p [B][H/2][H/2][64] = pool(relu(y)) and
 // arg (same shape, one byte each) = kh*3 + kw of the window's first maximum, 255 where it is <= 0.

@@ -51,7 +51,7 @@ class EagerTrainer:
         self.backend = backend
         # fused (hip_f32 backend only): ReLU + pool and the loss head on their HIP kernels (ops/f32.py
         # relu_pool / xent_head); False keeps them PyTorch ops -- the reference path of tools/f32_step_ab.py.
-        # conv2_impl (same backend): conv2's forward / data-gradient kernel, "direct" | "gemm" | None = the default
+        # conv2_impl (same backend): conv2's kernels, "direct_all" | "direct" | "gemm" | None = the default
         # ops/f32.py CONV2_IMPL_F32, set by the same-session A/B of tools/f32_conv_ab.py
         self.model = build_model(model, seed=seed, relu_logits=relu_logits, flat=flat_params,
                                  backend=backend, fused=fused, conv2_impl=conv2_impl).to(self.device)

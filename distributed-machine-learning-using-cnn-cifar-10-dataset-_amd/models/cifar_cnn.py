@@ -171,9 +171,10 @@ class CifarCNN(nn.Module):
         # fused (that backend only): ReLU + pool and the loss head on their HIP kernels too, else PyTorch ops
         self.backend = backend
         self.fused = bool(fused)
-        # conv2_impl (that backend only): conv2's forward / data-gradient kernel, "direct" | "gemm" | None
-        # (ops/f32.py CONV2_IMPL_F32); independent of fused
-        if conv2_impl not in (None, "direct", "gemm"):
+        # conv2_impl (that backend only): conv2's kernels, "direct_all" (forward, data and weight gradient
+        # direct) | "direct" (weight gradient on the GEMM) | "gemm" | None (ops/f32.py CONV2_IMPL_F32);
+        # independent of fused
+        if conv2_impl not in (None, "direct_all", "direct", "gemm"):
             raise ValueError(f"unknown conv2_impl {conv2_impl!r}")
         self.conv2_impl = conv2_impl
         if flat is None:

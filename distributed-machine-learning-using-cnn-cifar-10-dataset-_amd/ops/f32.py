@@ -7,8 +7,10 @@ matrix product of the step -- conv forward, conv weight/data gradients, the thre
 their gradients -- runs on ``torch.ops.dmlc.f32_gemm`` (fp32 MFMA ``v_mfma_f32_16x16x4_f32``, true
 fp32 operands, deterministic split-K).  The two convolutions are implicit GEMMs
 (``f32_conv_gemm``: the tile loader gathers the im2col matrix straight from the NHWC activation;
-conv2's forward and data gradient also have a direct kernel, ``f32_conv2_direct`` -- ``conv_same(impl=)``,
-``CONV2_IMPL_F32``):
+conv2 also has one direct kernel per role -- ``f32_conv2_direct`` for the forward and the data gradient,
+``f32_conv2_wgrad`` for the weight + bias gradient -- chosen by ``conv_same(impl=)`` / ``CONV2_IMPL_F32``:
+"direct" runs the first two on the direct kernel and keeps the weight gradient on the GEMM, "direct_all" runs
+all three direct):
 forward = im2col(x) W, weight + bias gradient = im2col(x)^T dY with a ones column (its output row
 is the bias gradient), data gradient = im2col(dY) against the flipped, transposed weight -- no
 column matrix is ever written.  Other geometries (e.g. another crop) use ``f32_im2col`` + GEMM with
@@ -103,19 +105,25 @@ class _ConvImplicit(torch.autograd.Function):
 # conv2's forward and data gradient on the fp32 step: "direct" (k_f32_conv2, csrc/kernels/f32_conv.hip) or
 # "gemm" (the implicit GEMM of f32_gemm.hip with a flipped, transposed weight copy per backward); set by the
 # same-session A/B of tools/f32_conv_ab.py: "direct" only if it wins at B = 256 by more than the larger spread
-# of the two paths (profiles/f32_conv_ab.txt: 0.769 ms/step direct against 0.922 ms gemm, spreads 0.047 / 0.043)
-CONV2_IMPL_F32 = "direct"
+# of the two paths (profiles/f32_conv_ab.txt: 0.769 ms/step direct against 0.922 ms gemm, spreads 0.047 / 0.043).
+# "direct_all" = "direct" with the weight + bias gradient on k_f32_conv2_wgrad too, under the same rule against
+# "direct" (profiles/f32_wgrad_ab.txt, B = 256: 0.606 ms/step direct_all against 0.760 ms direct, spreads
+# 0.064 / 0.054; B = 128: 0.478 against 0.556 ms, spreads 0.009 / 0.008)
+CONV2_IMPL_F32 = "direct_all"
+CONV2_IMPLS = ("direct_all", "direct", "gemm")
 
 
 class _ConvDirect(torch.autograd.Function):
     """conv2 ([B,12,12,64] -> 64 channels, 5x5 TF-'SAME') on k_f32_conv2: the image in LDS, the weights
     streamed as MFMA fragments; the data gradient reads the same HWIO weight in place (no flipped or
-    transposed copy).  The weight + bias gradient stays the implicit GEMM im2col(x)^T dY."""
+    transposed copy).  The weight + bias gradient is the implicit GEMM im2col(x)^T dY ("direct") or, with
+    ``wgrad_direct``, k_f32_conv2_wgrad ("direct_all"); both return the same [1601, 64] layout."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, wgrad_direct=False):
         x, w = x.contiguous(), w.contiguous()
         ctx.save_for_backward(x, w)
+        ctx.wgrad_direct = wgrad_direct
         return _ops().f32_conv2_direct(x, w, b.contiguous(), False)
 
     @staticmethod
@@ -123,9 +131,12 @@ class _ConvDirect(torch.autograd.Function):
         x, w = ctx.saved_tensors
         ops = _ops()
         gy = gy.contiguous()
-        gwb = ops.f32_conv_gemm(x, gy.view(-1, 64), None, True, True)            # [1601, 64]
+        if ctx.wgrad_direct:
+            gwb = ops.f32_conv2_wgrad(x, gy)                                     # [1601, 64]
+        else:
+            gwb = ops.f32_conv_gemm(x, gy.view(-1, 64), None, True, True)
         gx = ops.f32_conv2_direct(gy, w, None, True) if ctx.needs_input_grad[0] else None
-        return gx, gwb[:1600].view(5, 5, 64, 64), gwb[1600]
+        return gx, gwb[:1600].view(5, 5, 64, 64), gwb[1600], None
 
 
 class _ConvSame(torch.autograd.Function):
@@ -163,13 +174,16 @@ def linear(x, w, b):
 
 
 def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None):
-    """``impl``: "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernel of the [B,12,12,64] -> 64 geometry
-    (conv2); every other geometry takes the implicit / explicit GEMM path whatever ``impl`` says."""
-    if impl not in (None, "direct", "gemm"):
-        raise ValueError(f"conv_same: impl must be 'direct', 'gemm' or None, got {impl!r}")
-    if (impl or CONV2_IMPL_F32) == "direct" and (implicit or impl) and tuple(x.shape[1:]) == (12, 12, 64) \
+    """``impl``: "direct_all" | "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernels of the
+    [B,12,12,64] -> 64 geometry (conv2): all three roles direct, forward and data gradient direct with the
+    weight gradient on the GEMM, or all GEMM; every other geometry takes the implicit / explicit GEMM path
+    whatever ``impl`` says."""
+    if impl not in (None,) + CONV2_IMPLS:
+        raise ValueError(f"conv_same: impl must be one of {CONV2_IMPLS} or None, got {impl!r}")
+    use = impl or CONV2_IMPL_F32
+    if use != "gemm" and (implicit or impl) and tuple(x.shape[1:]) == (12, 12, 64) \
             and tuple(w.shape) == (5, 5, 64, 64):
-        return _ConvDirect.apply(x, w, b)
+        return _ConvDirect.apply(x, w, b, use == "direct_all")
     if implicit and w.shape[0] == 5 and w.shape[1] == 5 and (x.shape[1], x.shape[3]) in _IMPLICIT \
             and x.shape[1] == x.shape[2]:
         return _ConvImplicit.apply(x, w, b)

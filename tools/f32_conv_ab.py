@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Time the fp32 HIP training step on ONE GPU with conv2's forward and data gradient on the direct kernel
-(k_f32_conv2, csrc/kernels/f32_conv.hip) against the same step with both on the implicit GEMM:
+"""Time the fp32 HIP training step on ONE GPU with conv2 on its direct kernels (csrc/kernels/f32_conv.hip)
+against the same step with conv2 on the implicit GEMM:
    python tools/f32_conv_ab.py [--batches 256,128] [--steps 300] [--rounds 3] [--out FILE]
-Per batch size, two hip_f32 EagerTrainers on the same synthetic data and seed (conv2_impl="gemm" / "direct"),
-both graph-captured; after warm-up, --steps steps per path are timed in interleaved rounds (gemm, direct,
-direct, gemm, ...), each window between two device syncs; the minimum per path is kept and the per-round
-figures give the spread.  Both trainers have then run the same number of steps: the relative difference of
-their flat parameters is reported too.  Prints one JSON line per measurement and a summary line per batch
-size, and writes the summaries to --out.  ops/f32.py CONV2_IMPL_F32 follows "direct_wins_beyond_spread" at
+Per batch size, one hip_f32 EagerTrainer per path on the same synthetic data and seed -- conv2_impl="gemm",
+"direct" (forward and data gradient on k_f32_conv2) and "direct_all" (the weight gradient on
+k_f32_conv2_wgrad as well) --, all graph-captured; after warm-up, --steps steps per path are timed in
+interleaved rounds (gemm, direct, direct_all, direct_all, direct, gemm, ...), each window between two device
+syncs; the minimum per path is kept and the per-round figures give the spread.  All trainers have then run
+the same number of steps: the relative difference of their flat parameters to the GEMM path's is reported
+too.  Prints one JSON line per measurement and a summary line per batch size, and writes the summaries to
+--out.  ops/f32.py CONV2_IMPL_F32 follows "direct_wins_beyond_spread" (direct against gemm) and
+"direct_all_wins_beyond_spread" (direct_all against direct, by more than the larger spread of those two) at
 B = 256."""
 import argparse
 import json
@@ -21,7 +24,7 @@ import torch  # noqa: E402
 import dmlc  # noqa: E402,F401
 from dmlc.engine.eager import EagerTrainer  # noqa: E402
 
-PATHS = ("gemm", "direct")
+PATHS = ("gemm", "direct", "direct_all")
 
 
 def run(batch, steps, rounds, data, labels):
@@ -51,9 +54,13 @@ def run(batch, steps, rounds, data, labels):
             "ms_per_step_by_round": per_round, "min_ms_per_step": best, "spread_ms": spread,
             "images_per_s": {k: round(batch / v * 1e3) for k, v in best.items()},
             "speedup_direct_over_gemm": round(best["gemm"] / best["direct"], 3),
-            "direct_wins_beyond_spread": best["gemm"] - best["direct"] > max(spread.values()),
+            "direct_wins_beyond_spread": best["gemm"] - best["direct"] > max(spread["gemm"], spread["direct"]),
+            "speedup_direct_all_over_direct": round(best["direct"] / best["direct_all"], 3),
+            "direct_all_wins_beyond_spread":
+                best["direct"] - best["direct_all"] > max(spread["direct"], spread["direct_all"]),
             "steps_run_per_path": 20 + steps * rounds,
-            "flat_params_rel_diff": float((flat["direct"] - flat["gemm"]).norm() / flat["gemm"].norm()),
+            "flat_params_rel_diff": {k: float((flat[k] - flat["gemm"]).norm() / flat["gemm"].norm())
+                                     for k in PATHS[1:]},
             "last_loss": {k: float(tr.last_loss) for k, tr in trs.items()}}
 
 

@@ -137,3 +137,27 @@ def pool_reads(H, swap, grouped):
 
 for H in (24, 12):
     print(f"pool{1 if H == 24 else 2} reads: r4 {pool_reads(H, False, False):.1f}  swzpool + grouped lanes {pool_reads(H, True, True):.1f}")
+
+
+# --- fp32 conv2 weight gradient (f32_conv.hip k_f32_conv2_wgrad): one 4-byte word per lane ----------------
+# lane (q, r) of wave j reads word j of channel chunk r of padded pixel (py, px + q): passes per wave read
+# (1 = the 64 lanes hit 64 distinct banks) under the p1_off chunk swizzle of k_f32_conv2 and in the channel
+# planes the kernel uses (plane j = [16][16][16] words, word 16 * pixel + r).
+def wgrad_reads(off):
+    res = []
+    for j in range(4):
+        for py in range(16):
+            for px in range(13):
+                banks = {}
+                for l in range(64):
+                    dw = off(py, px + (l >> 4), l & 15, j)
+                    banks.setdefault(dw % 64, set()).add(dw)
+                res.append(max(len(v) for v in banks.values()))
+    return sum(res) / len(res), max(res)
+
+
+def p1_word(py, px, c, j): return (py * 16 + px) * 64 + ((c ^ ((px & 3) | ((py & 3) << 2))) << 2) + j
+def plane_word(py, px, c, j): return j * 4096 + (py * 16 + px) * 16 + c
+
+
+print("wgrad 4-byte reads (mean, worst passes): p1_off swizzle ->", wgrad_reads(p1_word), " channel planes ->", wgrad_reads(plane_word))
