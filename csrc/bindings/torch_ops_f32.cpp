@@ -1,4 +1,4 @@
-// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_conv.hip, f32_pool.hip): the building blocks
+// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_conv.hip, f32_conv1.hip, f32_pool.hip): the building blocks
 // of the fp32-accurate CNN path (ops/f32.py).  Functional ops (they allocate their outputs on the
 // caching allocator and launch on the current HIP stream, so they compose with autograd and are
 // capturable into HIP graphs); every launch is preceded by a full shape / dtype / layout check.
@@ -146,6 +146,50 @@ Tensor f32_conv2_wgrad(const Tensor& x, const Tensor& dy, int64_t groups) {
   CHECK_HIP(dmlc_f32_conv2_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), out.data_ptr<float>(), ws.data_ptr<float>(),
                                  (int)x.size(0), G, stream_of(x)));
   return out;
+}
+
+// Direct conv1 weight + bias gradient (f32_conv1.hip): x fp32 NHWC [B, 24, 24, 3] and the gradient at the conv
+// output -> [76, 64], the layout of f32_conv_gemm(x, dy, None, True, True).  f32_conv1_wgrad takes dy fp32
+// [B, 24, 24, 64]; f32_conv1_wgrad_pool takes the pooled gradient dp fp32 [B, 12, 12, 64] and the argmax bytes
+// of f32_relu_pool_fwd and rebuilds dy inside the kernel (f32_relu_pool_bwd's output, bit for bit, never in
+// memory).  groups: image groups = partial sums per element (0: the CU count, always clamped to B).
+Tensor conv1_wgrad(const char* op, const Tensor& x, const Tensor* dy, const Tensor* dp, const Tensor* arg, int64_t groups) {
+  f32_in(x, "x", 4);
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= (1 << 20) && x.size(1) == 24 && x.size(2) == 24 && x.size(3) == 3, op,
+              ": x must be [1 <= B <= 2^20, 24, 24, 3], got ", x.sizes());
+  const int64_t B = x.size(0);
+  const Tensor& g = dy ? *dy : *dp;
+  const char* gn = dy ? "dy" : "dp";
+  const int64_t H = dy ? 24 : 12;
+  check(g, gn, at::kFloat, {B, H, H, 64});
+  TORCH_CHECK(g.device() == x.device(), op, ": x and ", gn, " on different devices");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0, op,
+              ": x and ", gn, " must be 16-byte aligned");
+  const uint8_t* ap = nullptr;
+  if (arg) {
+    check(*arg, "arg", at::kByte, {B, 12, 12, 64});
+    TORCH_CHECK(arg->device() == x.device(), op, ": x and arg on different devices");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(arg->data_ptr()) % 16 == 0, op, ": arg must be 16-byte aligned");
+    ap = arg->data_ptr<uint8_t>();
+  }
+  TORCH_CHECK(groups >= 0 && groups < (1ll << 31), op, ": groups must be >= 0 (0: one per CU)");
+  const c10::DeviceGuard guard(x.device());
+  int G = 0;
+  size_t n = 0;
+  CHECK_HIP(dmlc_f32_conv1_wgrad_plan((int)B, (int)groups, &G, &n));
+  auto ws = at::empty({(int64_t)n}, x.options());
+  auto out = at::empty({76, 64}, x.options());
+  CHECK_HIP(dmlc_f32_conv1_wgrad(x.data_ptr<float>(), dy ? g.data_ptr<float>() : nullptr, dy ? nullptr : g.data_ptr<float>(),
+                                 ap, out.data_ptr<float>(), ws.data_ptr<float>(), (int)B, G, stream_of(x)));
+  return out;
+}
+
+Tensor f32_conv1_wgrad(const Tensor& x, const Tensor& dy, int64_t groups) {
+  return conv1_wgrad("f32_conv1_wgrad", x, &dy, nullptr, nullptr, groups);
+}
+
+Tensor f32_conv1_wgrad_pool(const Tensor& x, const Tensor& dp, const Tensor& arg, int64_t groups) {
+  return conv1_wgrad("f32_conv1_wgrad_pool", x, nullptr, &dp, &arg, groups);
 }
 
 Tensor f32_im2col(const Tensor& x, int64_t kh, int64_t kw, int64_t pad) {
@@ -330,6 +374,8 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
   m.def("f32_conv_gemm(Tensor x, Tensor w, Tensor? bias, bool ta, bool ones) -> Tensor");
   m.def("f32_conv2_direct(Tensor x, Tensor w, Tensor? bias, bool dgrad, int blocks=0) -> Tensor");
   m.def("f32_conv2_wgrad(Tensor x, Tensor dy, int groups=0) -> Tensor");
+  m.def("f32_conv1_wgrad(Tensor x, Tensor dy, int groups=0) -> Tensor");
+  m.def("f32_conv1_wgrad_pool(Tensor x, Tensor dp, Tensor arg, int groups=0) -> Tensor");
   m.def("f32_im2col(Tensor x, int kh, int kw, int pad) -> Tensor");
   m.def("f32_col2im(Tensor dcols, int B, int H, int W, int C, int kh, int kw, int pad) -> Tensor");
   m.def("f32_colsum(Tensor x) -> Tensor");
@@ -343,6 +389,8 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_conv_gemm", &f32_conv_gemm);
   m.impl("f32_conv2_direct", &f32_conv2_direct);
   m.impl("f32_conv2_wgrad", &f32_conv2_wgrad);
+  m.impl("f32_conv1_wgrad", &f32_conv1_wgrad);
+  m.impl("f32_conv1_wgrad_pool", &f32_conv1_wgrad_pool);
   m.impl("f32_im2col", &f32_im2col);
   m.impl("f32_col2im", &f32_col2im);
   m.impl("f32_colsum", &f32_colsum);

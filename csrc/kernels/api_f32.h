@@ -73,6 +73,19 @@ hipError_t dmlc_f32_conv2_wgrad_plan(int B, int groups, int* G, size_t* ws_float
 hipError_t dmlc_f32_conv2_wgrad(const float* x, const float* dy, float* out, float* ws, int B, int groups,
                                 hipStream_t s);
 
+// k_f32_conv1_wgrad + k_f32_conv1_reduce (csrc/kernels/f32_conv1.hip): conv1's weight and bias gradient, direct.
+// x fp32 NHWC [B][24][24][3] -> out [76][64]: row (kh*5 + kw)*3 + ci = dW[kh][kw][ci][:], row 75 = db (the layout
+// of dmlc_f32_gemm's conv = 1 weight gradient with the ones column).  The gradient at the conv output is either
+// dy [B][24][24][64] (dp and arg null) or, with dy null, rebuilt inside the kernel from the pooled gradient dp
+// [B][12][12][64] and the argmax bytes arg of dmlc_f32_relu_pool_fwd, bit-identical to dmlc_f32_relu_pool_bwd's
+// output (any byte value is safe: bytes are compared, never used as an address).  groups: image groups =
+// partial sums per output element, 0 = one per CU, clamped to B; bit-reproducible for a fixed (B, groups).
+// ws: the partials, written and read by this call only; _plan returns the group count G used and the floats
+// ws must hold.  Every pointer 16-byte aligned.
+hipError_t dmlc_f32_conv1_wgrad_plan(int B, int groups, int* G, size_t* ws_floats);
+hipError_t dmlc_f32_conv1_wgrad(const float* x, const float* dy, const float* dp, const uint8_t* arg, float* out,
+                                float* ws, int B, int groups, hipStream_t s);
+
 // csrc/kernels/f32_pool.hip: the ReLU + TF-SAME 3x3/2 max-pool of a conv stage and the loss head.
 // k_f32_relu_pool_fwd: y NHWC [B][H][H][64] (H = 24 or 12) -> p [B][H/2][H/2][64] = pool(relu(y)) and
 // arg (same shape, one byte each) = kh*3 + kw of the window's first maximum, 255 where it is <= 0.

@@ -163,7 +163,8 @@ class CifarCNN(nn.Module):
     specs = PARAM_SPECS
 
     def __init__(self, flat: torch.Tensor | None = None, relu_logits: bool = True, seed: int = 0,
-                 backend: str = "torch", fused: bool = True, conv2_impl: str | None = None):
+                 backend: str = "torch", fused: bool = True, conv2_impl: str | None = None,
+                 conv1_impl: str | None = None):
         super().__init__()
         if backend not in ("torch", "hip_f32"):
             raise ValueError(f"unknown CNN backend {backend!r}")
@@ -177,6 +178,11 @@ class CifarCNN(nn.Module):
         if conv2_impl not in (None, "direct_all", "direct", "gemm"):
             raise ValueError(f"unknown conv2_impl {conv2_impl!r}")
         self.conv2_impl = conv2_impl
+        # conv1_impl (that backend only): conv1's backward, "direct" (csrc/kernels/f32_conv1.hip) | "gemm" | None
+        # (ops/f32.py CONV1_IMPL_F32)
+        if conv1_impl not in (None, "direct", "gemm"):
+            raise ValueError(f"unknown conv1_impl {conv1_impl!r}")
+        self.conv1_impl = conv1_impl
         if flat is None:
             g = torch.Generator().manual_seed(seed)
             flat = init_flat_params(g)
@@ -190,7 +196,7 @@ class CifarCNN(nn.Module):
         if self.backend == "hip_f32":
             from ..ops.f32 import cnn_forward_f32, flat_views
             return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits, self.fused,
-                                   self.conv2_impl)
+                                   self.conv2_impl, self.conv1_impl)
         return cnn_forward(images_nhwc, self.params(), self.relu_logits)
 
     def loss_and_hits(self, images_nhwc: torch.Tensor, labels: torch.Tensor):
@@ -200,7 +206,8 @@ class CifarCNN(nn.Module):
         if self.backend != "hip_f32":
             raise ValueError("loss_and_hits is the hip_f32 backend's loss head")
         from ..ops.f32 import cnn_forward_f32, flat_views, xent_head
-        raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused, self.conv2_impl)
+        raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused, self.conv2_impl,
+                              self.conv1_impl)
         return xent_head(raw, labels.view(-1), self.relu_logits)
 
     def named_tf_variables(self) -> Dict[str, torch.Tensor]:

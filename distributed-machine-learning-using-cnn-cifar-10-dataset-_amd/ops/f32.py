@@ -13,7 +13,12 @@ conv2 also has one direct kernel per role -- ``f32_conv2_direct`` for the forwar
 all three direct):
 forward = im2col(x) W, weight + bias gradient = im2col(x)^T dY with a ones column (its output row
 is the bias gradient), data gradient = im2col(dY) against the flipped, transposed weight -- no
-column matrix is ever written.  Other geometries (e.g. another crop) use ``f32_im2col`` + GEMM with
+column matrix is ever written.  conv1 has no data gradient (its input is the image), and its backward has a
+direct kernel family too (csrc/kernels/f32_conv1.hip, ``CONV1_IMPL_F32`` / ``conv1_impl`` = "direct"): with
+``fused`` the whole first stage is one autograd function whose backward is ONE call of ``f32_conv1_wgrad_pool`` --
+the kernel rebuilds the gradient at the conv output from the pooled gradient and the argmax bytes in LDS
+(``f32_relu_pool_bwd``'s result, bit for bit) and never writes it to memory --, without ``fused`` the weight
+gradient of the [B,24,24,3] geometry runs on ``f32_conv1_wgrad``; "gemm" keeps the implicit GEMM.  Other geometries (e.g. another crop) use ``f32_im2col`` + GEMM with
 the gather-form ``f32_col2im`` adjoint.  fc bias gradients: ``f32_colsum``.
 
 The rest of the step is HIP as well (csrc/kernels/f32_pool.hip): ``relu_pool`` is the ReLU + TF-SAME 3x3/2
@@ -72,7 +77,7 @@ class _ConvImplicit(torch.autograd.Function):
     """Stride-1 TF-'SAME' 5x5 convolution as implicit GEMMs (no column matrix in memory)."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, wgrad_direct=False):
         ops = _ops()
         B, H, W, C = x.shape
         co = w.shape[3]
@@ -80,6 +85,7 @@ class _ConvImplicit(torch.autograd.Function):
         wm = w.contiguous().view(25 * C, co)
         y = ops.f32_conv_gemm(x, wm, b.contiguous(), False, False)
         ctx.save_for_backward(x, w)
+        ctx.wgrad_direct = wgrad_direct and (H, C, co) == (24, 3, 64)    # the geometry of k_f32_conv1_wgrad
         return y.view(B, H, W, co)
 
     @staticmethod
@@ -89,7 +95,10 @@ class _ConvImplicit(torch.autograd.Function):
         B, H, W, C = x.shape
         co = w.shape[3]
         gy = gy.contiguous()
-        gwb = ops.f32_conv_gemm(x, gy.view(B * H * W, co), None, True, True)   # [25*C + 1, co]
+        if ctx.wgrad_direct:
+            gwb = ops.f32_conv1_wgrad(x, gy)                                     # [76, 64], the same layout
+        else:
+            gwb = ops.f32_conv_gemm(x, gy.view(B * H * W, co), None, True, True)   # [25*C + 1, co]
         gw, gb = gwb[:25 * C].view(5, 5, C, co), gwb[25 * C]
         gx = None
         if ctx.needs_input_grad[0] and (H, co) in _IMPLICIT:
@@ -99,7 +108,7 @@ class _ConvImplicit(torch.autograd.Function):
         elif ctx.needs_input_grad[0]:          # dY geometry without an implicit kernel: explicit adjoint
             dcols = ops.f32_gemm(gy.view(B * H * W, co), w.contiguous().view(25 * C, co), None, False, True, False)
             gx = ops.f32_col2im(dcols, B, H, W, C, 5, 5, 2)
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
 # conv2's forward and data gradient on the fp32 step: "direct" (k_f32_conv2, csrc/kernels/f32_conv.hip) or
@@ -111,6 +120,42 @@ class _ConvImplicit(torch.autograd.Function):
 # 0.064 / 0.054; B = 128: 0.478 against 0.556 ms, spreads 0.009 / 0.008)
 CONV2_IMPL_F32 = "direct_all"
 CONV2_IMPLS = ("direct_all", "direct", "gemm")
+
+
+# conv1's backward on the fp32 step: "direct" (csrc/kernels/f32_conv1.hip: with fused the pool + ReLU backward and
+# the weight gradient in one launch, without it the weight gradient alone) or "gemm" (f32_relu_pool_bwd + the
+# implicit GEMM); under the rule above on tools/f32_conv_ab.py --stage conv1
+# (profiles/f32_conv1_ab.txt, B = 256: 0.503 ms/step direct against 0.637 ms gemm, spreads 0.006 / 0.042; B = 128:
+# 0.425 against 0.486 ms, spreads 0.008 / 0.038)
+CONV1_IMPL_F32 = "direct"
+CONV1_IMPLS = ("direct", "gemm")
+
+
+def _conv1_impl(impl: Optional[str]) -> str:
+    if impl not in (None,) + CONV1_IMPLS:
+        raise ValueError(f"conv1_impl must be one of {CONV1_IMPLS} or None, got {impl!r}")
+    return impl or CONV1_IMPL_F32
+
+
+class _Conv1Stage(torch.autograd.Function):
+    """The whole first stage pool(relu(conv1(x) + b)) of an image batch x [B,24,24,3] that needs no gradient.
+    Forward: the kernels of the "gemm" path (f32_conv_gemm + f32_relu_pool_fwd, the same bits).  Saves x and the
+    one-byte argmax only; the backward is one call of f32_conv1_wgrad_pool."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ops = _ops()
+        x = x.contiguous()
+        y = ops.f32_conv_gemm(x, w.contiguous().view(75, 64), b.contiguous(), False, False)
+        p, arg = ops.f32_relu_pool_fwd(y.view(x.shape[0], 24, 24, 64), 0)
+        ctx.save_for_backward(x, arg)
+        return p
+
+    @staticmethod
+    def backward(ctx, gp):
+        x, arg = ctx.saved_tensors
+        gwb = _ops().f32_conv1_wgrad_pool(x, gp.contiguous(), arg)               # [76, 64]
+        return None, gwb[:75].view(5, 5, 3, 64), gwb[75]
 
 
 class _ConvDirect(torch.autograd.Function):
@@ -173,8 +218,9 @@ def linear(x, w, b):
     return _Linear.apply(x, w, b)
 
 
-def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None):
-    """``impl``: "direct_all" | "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernels of the
+def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None, conv1_impl: Optional[str] = None):
+    """``conv1_impl``: "direct" | "gemm" | None (``CONV1_IMPL_F32``) -- the weight-gradient kernel of the
+    [B,24,24,3] -> 64 geometry (conv1) on the implicit path.  ``impl``: "direct_all" | "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernels of the
     [B,12,12,64] -> 64 geometry (conv2): all three roles direct, forward and data gradient direct with the
     weight gradient on the GEMM, or all GEMM; every other geometry takes the implicit / explicit GEMM path
     whatever ``impl`` says."""
@@ -186,7 +232,7 @@ def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None):
         return _ConvDirect.apply(x, w, b, use == "direct_all")
     if implicit and w.shape[0] == 5 and w.shape[1] == 5 and (x.shape[1], x.shape[3]) in _IMPLICIT \
             and x.shape[1] == x.shape[2]:
-        return _ConvImplicit.apply(x, w, b)
+        return _ConvImplicit.apply(x, w, b, _conv1_impl(conv1_impl) == "direct")
     return _ConvSame.apply(x, w, b)
 
 
@@ -318,21 +364,26 @@ def cnn_infer_f32(images_u8: torch.Tensor, flat: torch.Tensor, labels: Optional[
     return logits, pred, hits
 
 
-def _conv_stage(x, w, b, fused: bool, impl: Optional[str] = None):
-    y = conv_same(x, w, b, impl=impl)
+def _conv_stage(x, w, b, fused: bool, impl: Optional[str] = None, conv1_impl: Optional[str] = None):
+    if fused and _conv1_impl(conv1_impl) == "direct" and not x.requires_grad \
+            and tuple(x.shape[1:]) == (24, 24, 3) and tuple(w.shape) == (5, 5, 3, 64):
+        return _Conv1Stage.apply(x, w, b)
+    y = conv_same(x, w, b, impl=impl, conv1_impl=conv1_impl)
     if fused and y.shape[1] == y.shape[2] and y.shape[1] in _FUSED_POOL and y.shape[3] == 64:
         return relu_pool(y)
     return _pool_nhwc(torch.relu(y))
 
 
 def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True,
-                    fused: bool = True, conv2_impl: Optional[str] = None) -> torch.Tensor:
+                    fused: bool = True, conv2_impl: Optional[str] = None,
+                    conv1_impl: Optional[str] = None) -> torch.Tensor:
     """The reference CNN (models/cifar_cnn.py:cnn_forward semantics) on the fp32 HIP kernels.  ``fused``:
     ReLU + pool of the conv stages through ``relu_pool`` where the geometry is one of its two ([B,24,24,64],
     [B,12,12,64]); otherwise, and with ``fused=False``, the PyTorch ops (same logits bit for bit).
-    ``conv2_impl``: the second stage's conv kernel, ``conv_same``'s ``impl`` (independent of ``fused``)."""
+    ``conv2_impl``: the second stage's conv kernel, ``conv_same``'s ``impl`` (independent of ``fused``); ``conv1_impl``: the
+    first stage's backward, "direct" | "gemm" | None (``CONV1_IMPL_F32``)."""
     x = images_nhwc.float().contiguous()
-    x = _conv_stage(x, p["conv1_kernel"], p["conv1_bias"], fused)
+    x = _conv_stage(x, p["conv1_kernel"], p["conv1_bias"], fused, conv1_impl=conv1_impl)
     x = _conv_stage(x, p["conv2_kernel"], p["conv2_bias"], fused, conv2_impl)
     x = x.reshape(x.shape[0], -1)                               # NHWC flatten (cifar10cnn.py:126)
     x = torch.relu(linear(x, p["full_weight_1"], p["full_bias_1"]))

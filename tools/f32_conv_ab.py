@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the fp32 HIP training step on ONE GPU with conv2 on its direct kernels (csrc/kernels/f32_conv.hip)
 against the same step with conv2 on the implicit GEMM:
-   python tools/f32_conv_ab.py [--batches 256,128] [--steps 300] [--rounds 3] [--out FILE]
+   python tools/f32_conv_ab.py [--stage conv2|conv1] [--batches 256,128] [--steps 300] [--rounds 3] [--out FILE]
 Per batch size, one hip_f32 EagerTrainer per path on the same synthetic data and seed -- conv2_impl="gemm",
 "direct" (forward and data gradient on k_f32_conv2) and "direct_all" (the weight gradient on
 k_f32_conv2_wgrad as well) --, all graph-captured; after warm-up, --steps steps per path are timed in
@@ -11,7 +11,10 @@ the same number of steps: the relative difference of their flat parameters to th
 too.  Prints one JSON line per measurement and a summary line per batch size, and writes the summaries to
 --out.  ops/f32.py CONV2_IMPL_F32 follows "direct_wins_beyond_spread" (direct against gemm) and
 "direct_all_wins_beyond_spread" (direct_all against direct, by more than the larger spread of those two) at
-B = 256."""
+B = 256.
+--stage conv1 times conv1's backward instead (conv2 on its default): conv1_impl="gemm" (f32_relu_pool_bwd + the
+implicit GEMM) against "direct" (one launch of k_f32_conv1_wgrad, csrc/kernels/f32_conv1.hip); ops/f32.py
+CONV1_IMPL_F32 follows its "direct_wins_beyond_spread" at B = 256."""
 import argparse
 import json
 import os
@@ -24,12 +27,13 @@ import torch  # noqa: E402
 import dmlc  # noqa: E402,F401
 from dmlc.engine.eager import EagerTrainer  # noqa: E402
 
-PATHS = ("gemm", "direct", "direct_all")
+STAGES = {"conv2": ("conv2_impl", ("gemm", "direct", "direct_all")), "conv1": ("conv1_impl", ("gemm", "direct"))}
 
 
-def run(batch, steps, rounds, data, labels):
+def run(batch, steps, rounds, data, labels, stage="conv2"):
+    key, PATHS = STAGES[stage]
     kw = dict(device="cuda:0", dtype="fp32", lr=1e-5, seed=1, backend="hip_f32", graph=True)
-    trs = {name: EagerTrainer("cifar_cnn", batch, data, labels, conv2_impl=name, **kw) for name in PATHS}
+    trs = {name: EagerTrainer("cifar_cnn", batch, data, labels, **{key: name}, **kw) for name in PATHS}
     for tr in trs.values():                                   # 3 eager warm-up steps, capture, replays
         for _ in range(20):
             tr.step()
@@ -46,26 +50,29 @@ def run(batch, steps, rounds, data, labels):
             torch.cuda.synchronize()
             ms = 1e3 * (time.perf_counter() - t0) / steps
             per_round[name].append(round(ms, 4))
-            print(json.dumps({"batch": batch, "path": name, "round": r, "ms_per_step": round(ms, 4)}), flush=True)
+            print(json.dumps({"batch": batch, "stage": stage, "path": name, "round": r, "ms_per_step": round(ms, 4)}), flush=True)
     best = {k: min(v) for k, v in per_round.items()}
     spread = {k: round(max(v) - min(v), 4) for k, v in per_round.items()}
     flat = {k: tr.model.flat.detach().double() for k, tr in trs.items()}
-    return {"batch": batch, "dtype": "fp32", "steps": steps, "rounds": rounds, "graph": True,
-            "ms_per_step_by_round": per_round, "min_ms_per_step": best, "spread_ms": spread,
-            "images_per_s": {k: round(batch / v * 1e3) for k, v in best.items()},
-            "speedup_direct_over_gemm": round(best["gemm"] / best["direct"], 3),
-            "direct_wins_beyond_spread": best["gemm"] - best["direct"] > max(spread["gemm"], spread["direct"]),
-            "speedup_direct_all_over_direct": round(best["direct"] / best["direct_all"], 3),
-            "direct_all_wins_beyond_spread":
-                best["direct"] - best["direct_all"] > max(spread["direct"], spread["direct_all"]),
-            "steps_run_per_path": 20 + steps * rounds,
-            "flat_params_rel_diff": {k: float((flat[k] - flat["gemm"]).norm() / flat["gemm"].norm())
-                                     for k in PATHS[1:]},
-            "last_loss": {k: float(tr.last_loss) for k, tr in trs.items()}}
+    out = {"batch": batch, "stage": stage, "dtype": "fp32", "steps": steps, "rounds": rounds, "graph": True,
+           "ms_per_step_by_round": per_round, "min_ms_per_step": best, "spread_ms": spread,
+           "images_per_s": {k: round(batch / v * 1e3) for k, v in best.items()},
+           "speedup_direct_over_gemm": round(best["gemm"] / best["direct"], 3),
+           "direct_wins_beyond_spread": best["gemm"] - best["direct"] > max(spread["gemm"], spread["direct"])}
+    if stage == "conv2":
+        out.update({"speedup_direct_all_over_direct": round(best["direct"] / best["direct_all"], 3),
+                    "direct_all_wins_beyond_spread":
+                        best["direct"] - best["direct_all"] > max(spread["direct"], spread["direct_all"])})
+    out.update({"steps_run_per_path": 20 + steps * rounds,
+                "flat_params_rel_diff": {k: float((flat[k] - flat["gemm"]).norm() / flat["gemm"].norm())
+                                         for k in PATHS[1:]},
+                "last_loss": {k: float(tr.last_loss) for k, tr in trs.items()}})
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stage", default="conv2", choices=sorted(STAGES))
     ap.add_argument("--batches", default="256,128")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--rounds", type=int, default=3)
@@ -75,7 +82,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     data = torch.randint(0, 256, (8192, 32, 32, 3), dtype=torch.uint8, generator=g)
     labels = torch.randint(0, 10, (8192,), dtype=torch.int32, generator=g)
-    summaries = [run(int(b), a.steps, a.rounds, data, labels) for b in a.batches.split(",")]
+    summaries = [run(int(b), a.steps, a.rounds, data, labels, a.stage) for b in a.batches.split(",")]
     for s in summaries:
         print(json.dumps(s), flush=True)
     if a.out:

@@ -161,3 +161,40 @@ def plane_word(py, px, c, j): return j * 4096 + (py * 16 + px) * 16 + c
 
 
 print("wgrad 4-byte reads (mean, worst passes): p1_off swizzle ->", wgrad_reads(p1_word), " channel planes ->", wgrad_reads(plane_word))
+
+
+# --- fp32 conv1 backward (f32_conv1.hip k_f32_conv1_wgrad): one 4-byte word per lane, both operands -----------
+# First operand: lane (q, r) of row tile t reads im2col row m = 16 t + r of pixel (y, x0 + q) of the zero-padded
+# [28][pitch] image, word (y + kh) * pitch + (x0 + q + kw) * 3 + ci (rows 75 .. 79 read word 0 and are replaced);
+# equal words are one broadcast.  Second operand: word 16 * (pixel + q) + r of channel-tile plane nt against the
+# pixel-major band [pixel][64].
+def conv1_x_reads(pitch):
+    res = []
+    for t in range(5):
+        for y in range(24):
+            for x0 in range(0, 24, 4):
+                banks = {}
+                for l in range(64):
+                    q, m = l >> 4, 16 * t + (l & 15)
+                    tap, ci = divmod(min(m, 74), 3)
+                    dw = (y + tap // 5) * pitch + (x0 + q + tap % 5) * 3 + ci if m < 75 else 0
+                    banks.setdefault(dw % 64, set()).add(dw)
+                res.append(max(len(v) for v in banks.values()))
+    return sum(res) / len(res), max(res)
+
+
+def conv1_dy_reads(off):
+    res = []
+    for nt in range(4):
+        for pix in range(0, 144, 4):
+            banks = {}
+            for l in range(64):
+                dw = off(pix + (l >> 4), nt, l & 15)
+                banks.setdefault(dw % 64, set()).add(dw)
+            res.append(max(len(v) for v in banks.values()))
+    return sum(res) / len(res), max(res)
+
+
+print("conv1 wgrad x reads (mean, worst passes): pitch 84 ->", conv1_x_reads(84), " pitch 88 ->", conv1_x_reads(88))
+print("conv1 wgrad dy reads (mean, worst passes): [pixel][64] ->", conv1_dy_reads(lambda p, nt, r: p * 64 + 16 * nt + r),
+      " channel-tile planes ->", conv1_dy_reads(lambda p, nt, r: nt * 2320 + p * 16 + r))
