@@ -1,4 +1,4 @@
-// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_conv.hip, f32_conv1.hip, f32_pool.hip): the building blocks
+// torch.ops.dmlc.f32_* bindings of the fp32 kernels (csrc/kernels/f32_gemm.hip, f32_conv.hip, f32_conv1.hip, f32_pool.hip, f32_fc.hip): the building blocks
 // of the fp32-accurate CNN path (ops/f32.py).  Functional ops (they allocate their outputs on the
 // caching allocator and launch on the current HIP stream, so they compose with autograd and are
 // capturable into HIP graphs); every launch is preceded by a full shape / dtype / layout check.
@@ -289,6 +289,86 @@ std::tuple<Tensor, Tensor, Tensor> f32_xent_head(const Tensor& logits, const Ten
   return {loss, hits, dl};
 }
 
+// The fc stack behind fc1's forward (f32_fc.hip), 2304 -> 384 -> 192 -> 10, weights [in, out].  fc_arg: one
+// operand checked in full -- GPU, contiguous, fp32, the exact shape, on `on`'s device, `align`-byte aligned.
+void fc_arg(const char* op, const Tensor& t, const char* n, std::vector<int64_t> shape, const Tensor& on, int align) {
+  check(t, n, at::kFloat, std::move(shape));
+  TORCH_CHECK(t.device() == on.device(), op, ": ", n, " is on another device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % align == 0, op, ": ", n, " must be ", align, "-byte aligned");
+}
+
+int64_t fc_batch(const char* op, const Tensor& t, const char* n, int64_t cols) {
+  TORCH_CHECK(t.dim() == 2 && t.size(1) == cols && t.size(0) >= 1 && t.size(0) <= DMLC_F32_FC_MAX_B, op, ": ", n,
+              " must be [1 <= B <= 2^19, ", cols, "], got ", t.sizes());
+  return t.size(0);
+}
+
+// h1 [B, 384] = relu(x W1 + b1) -> (h2 [B, 192] = relu(h1 W2 + b2), logits [B, 10] = h2 W3 + b3)
+std::tuple<Tensor, Tensor> f32_fc_tail_fwd(const Tensor& h1, const Tensor& w2, const Tensor& b2, const Tensor& w3,
+                                           const Tensor& b3) {
+  const char* op = "f32_fc_tail_fwd";
+  const int64_t B = fc_batch(op, h1, "h1", 384);
+  fc_arg(op, h1, "h1", {B, 384}, h1, 16);
+  fc_arg(op, w2, "w2", {384, 192}, h1, 16);
+  fc_arg(op, b2, "b2", {192}, h1, 16);
+  fc_arg(op, w3, "w3", {192, 10}, h1, 4);
+  fc_arg(op, b3, "b3", {10}, h1, 4);
+  const c10::DeviceGuard g(h1.device());
+  auto h2 = at::empty({B, 192}, h1.options());
+  auto logits = at::empty({B, 10}, h1.options());
+  CHECK_HIP(dmlc_f32_fc_tail_fwd(h1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(), w3.data_ptr<float>(),
+                                 b3.data_ptr<float>(), h2.data_ptr<float>(), logits.data_ptr<float>(), (int)B,
+                                 stream_of(h1)));
+  return {h2, logits};
+}
+
+// -> (dh2 [B, 192] = (dlogits W3^T) where h2 > 0, dh1 [B, 384] = (dh2 W2^T) where h1 > 0; 0 elsewhere)
+std::tuple<Tensor, Tensor> f32_fc_tail_bwd(const Tensor& dlogits, const Tensor& h1, const Tensor& h2, const Tensor& w2,
+                                           const Tensor& w3) {
+  const char* op = "f32_fc_tail_bwd";
+  const int64_t B = fc_batch(op, dlogits, "dlogits", 10);
+  fc_arg(op, dlogits, "dlogits", {B, 10}, dlogits, 4);
+  fc_arg(op, h1, "h1", {B, 384}, dlogits, 16);
+  fc_arg(op, h2, "h2", {B, 192}, dlogits, 16);
+  fc_arg(op, w2, "w2", {384, 192}, dlogits, 16);
+  fc_arg(op, w3, "w3", {192, 10}, dlogits, 4);
+  const c10::DeviceGuard g(dlogits.device());
+  auto dh2 = at::empty({B, 192}, h1.options());
+  auto dh1 = at::empty({B, 384}, h1.options());
+  CHECK_HIP(dmlc_f32_fc_tail_bwd(dlogits.data_ptr<float>(), h1.data_ptr<float>(), h2.data_ptr<float>(),
+                                 w2.data_ptr<float>(), w3.data_ptr<float>(), dh2.data_ptr<float>(), dh1.data_ptr<float>(),
+                                 (int)B, stream_of(dlogits)));
+  return {dh2, dh1};
+}
+
+// One launch -> (gw1b [2305, 384] = x^T dh1, gw2b [385, 192] = h1^T dh2, gw3b [193, 10] = h2^T dlogits, each with
+// the bias gradient as its last row; dx [B, 2304] = dh1 W1^T, or None without need_dx)
+std::tuple<Tensor, Tensor, Tensor, c10::optional<Tensor>> f32_fc_grads(const Tensor& x, const Tensor& h1, const Tensor& h2,
+                                                                       const Tensor& dh1, const Tensor& dh2,
+                                                                       const Tensor& dlogits, const Tensor& w1,
+                                                                       bool need_dx) {
+  const char* op = "f32_fc_grads";
+  const int64_t B = fc_batch(op, x, "x", 2304);
+  fc_arg(op, x, "x", {B, 2304}, x, 16);
+  fc_arg(op, h1, "h1", {B, 384}, x, 16);
+  fc_arg(op, h2, "h2", {B, 192}, x, 16);
+  fc_arg(op, dh1, "dh1", {B, 384}, x, 16);
+  fc_arg(op, dh2, "dh2", {B, 192}, x, 16);
+  fc_arg(op, dlogits, "dlogits", {B, 10}, x, 4);
+  fc_arg(op, w1, "w1", {2304, 384}, x, 16);
+  const c10::DeviceGuard g(x.device());
+  auto g1 = at::empty({2305, 384}, x.options());
+  auto g2 = at::empty({385, 192}, x.options());
+  auto g3 = at::empty({193, 10}, x.options());
+  c10::optional<Tensor> dx;
+  if (need_dx) dx = at::empty({B, 2304}, x.options());
+  CHECK_HIP(dmlc_f32_fc_grads(x.data_ptr<float>(), h1.data_ptr<float>(), h2.data_ptr<float>(), dh1.data_ptr<float>(),
+                              dh2.data_ptr<float>(), dlogits.data_ptr<float>(), w1.data_ptr<float>(), g1.data_ptr<float>(),
+                              g2.data_ptr<float>(), g3.data_ptr<float>(), need_dx ? dx->data_ptr<float>() : nullptr, (int)B,
+                              stream_of(x)));
+  return {g1, g2, g3, dx};
+}
+
 // The whole eval-mode forward in true fp32, one launch (f32_infer.hip): image i is data[idx[i]] (idx None:
 // data[i], N = data rows); writes logits [N, 10] and, when given, pred [N] and correct [N] (needs labels,
 // one per data row).  flat: the model's fp32 parameter buffer, off: the element offsets of its ten TF-layout
@@ -382,6 +462,10 @@ TORCH_LIBRARY_FRAGMENT(dmlc, m) {
   m.def("f32_relu_pool_fwd(Tensor y, int blocks=0) -> (Tensor, Tensor)");
   m.def("f32_relu_pool_bwd(Tensor dp, Tensor arg, int blocks=0) -> Tensor");
   m.def("f32_xent_head(Tensor logits, Tensor labels, bool relu_logits) -> (Tensor, Tensor, Tensor)");
+  m.def("f32_fc_tail_fwd(Tensor h1, Tensor w2, Tensor b2, Tensor w3, Tensor b3) -> (Tensor, Tensor)");
+  m.def("f32_fc_tail_bwd(Tensor dlogits, Tensor h1, Tensor h2, Tensor w2, Tensor w3) -> (Tensor, Tensor)");
+  m.def("f32_fc_grads(Tensor x, Tensor h1, Tensor h2, Tensor dh1, Tensor dh2, Tensor dlogits, Tensor w1, "
+        "bool need_dx) -> (Tensor, Tensor, Tensor, Tensor?)");
 }
 
 TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
@@ -397,5 +481,8 @@ TORCH_LIBRARY_IMPL(dmlc, CUDA, m) {
   m.impl("f32_relu_pool_fwd", &f32_relu_pool_fwd);
   m.impl("f32_relu_pool_bwd", &f32_relu_pool_bwd);
   m.impl("f32_xent_head", &f32_xent_head);
+  m.impl("f32_fc_tail_fwd", &f32_fc_tail_fwd);
+  m.impl("f32_fc_tail_bwd", &f32_fc_tail_bwd);
+  m.impl("f32_fc_grads", &f32_fc_grads);
   m.impl("f32_cnn_infer", &f32_cnn_infer);
 }

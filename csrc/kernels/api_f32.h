@@ -102,4 +102,21 @@ hipError_t dmlc_f32_relu_pool_bwd(const float* dp, const uint8_t* arg, float* dy
 hipError_t dmlc_f32_xent_head(const float* logits, const void* labels, int labels64, float* dlogits, float* loss,
                               int* hits, int B, int relu_logits, hipStream_t s);
 
+// csrc/kernels/f32_fc.hip: the fc stack 2304 -> 384 -> 192 -> 10 behind fc1's forward, weights in the TF layout
+// [in][out].  1 <= B <= DMLC_F32_FC_MAX_B; every pointer 16-byte aligned except w3, b3, logits and dlogits
+// (4 bytes: their rows are 40 bytes).  No launch waits on another workgroup; all results are bit-reproducible.
+#define DMLC_F32_FC_MAX_B (1 << 19)
+// k_f32_fc_tail_fwd: h1 [B][384] = relu(x W1 + b1) -> h2 [B][192] = relu(h1 W2 + b2), logits [B][10] = h2 W3 + b3.
+hipError_t dmlc_f32_fc_tail_fwd(const float* h1, const float* w2, const float* b2, const float* w3, const float* b3,
+                                float* h2, float* logits, int B, hipStream_t s);
+// k_f32_fc_tail_bwd: dh2 [B][192] = (dlogits W3^T) where h2 > 0, else 0; dh1 [B][384] = (dh2 W2^T) where h1 > 0.
+hipError_t dmlc_f32_fc_tail_bwd(const float* dlogits, const float* h1, const float* h2, const float* w2, const float* w3,
+                                float* dh2, float* dh1, int B, hipStream_t s);
+// k_f32_fc_grads, one launch: g1 [2305][384] = x^T dh1, g2 [385][192] = h1^T dh2, g3 [193][10] = h2^T dlogits, the
+// last row of each the bias gradient (the column sums of dh1 / dh2 / dlogits); dx [B][2304] = dh1 W1^T, skipped
+// when dx is null.  x [B][2304].
+hipError_t dmlc_f32_fc_grads(const float* x, const float* h1, const float* h2, const float* dh1, const float* dh2,
+                             const float* dlogits, const float* w1, float* g1, float* g2, float* g3, float* dx, int B,
+                             hipStream_t s);
+
 }  // extern "C"

@@ -41,10 +41,12 @@ RT_LIB = os.path.join(LIB_DIR, "_dmlc_rt" + (sysconfig.get_config_var("EXT_SUFFI
 # extra hipcc flags of single kernel files.  resnet_infer.hip, cnn_infer.hip, f32_infer.hip: scalar fp32
 # VALU only (no packed fp32 pairs), so an image's logits cannot depend on how the compiler paired the
 # epilogue's values; f32_pool.hip likewise (the pool backward's sums and the loss head's rows), and
-# f32_conv.hip (the K-half sum and the bias of its epilogue) and f32_conv1.hip (the pool-backward sums it repeats)
+# f32_conv.hip (the K-half sum and the bias of its epilogue) and f32_conv1.hip (the pool-backward sums it repeats),
+# and f32_fc.hip (the K-half sum + bias of fc2 and the bias-gradient column sums)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"resnet_infer.hip": _NO_PK_F32, "cnn_infer.hip": _NO_PK_F32, "f32_infer.hip": _NO_PK_F32,
-                  "f32_pool.hip": _NO_PK_F32, "f32_conv.hip": _NO_PK_F32, "f32_conv1.hip": _NO_PK_F32}
+                  "f32_pool.hip": _NO_PK_F32, "f32_conv.hip": _NO_PK_F32, "f32_conv1.hip": _NO_PK_F32,
+                  "f32_fc.hip": _NO_PK_F32}
 
 
 def _torch_paths():

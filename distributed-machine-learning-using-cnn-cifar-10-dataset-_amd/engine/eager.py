@@ -36,7 +36,8 @@ class EagerTrainer:
                  crop: int = C.CROP_HEIGHT, seed: int = 0, flat_params: Optional[torch.Tensor] = None,
                  augment: bool = False, graph: bool = False, warmup_steps: int = 0, backend: str = "torch",
                  momentum: float = 0.0, weight_decay: float = 0.0, fused: bool = True,
-                 conv2_impl: Optional[str] = None, conv1_impl: Optional[str] = None):
+                 conv2_impl: Optional[str] = None, conv1_impl: Optional[str] = None,
+                 fc_impl: Optional[str] = None):
         self.device = torch.device(device)
         if not 0.0 <= momentum < 1.0 or weight_decay < 0.0:
             raise ValueError("momentum must be in [0, 1) and weight_decay >= 0")
@@ -53,10 +54,11 @@ class EagerTrainer:
         # relu_pool / xent_head); False keeps them PyTorch ops -- the reference path of tools/f32_step_ab.py.
         # conv2_impl (same backend): conv2's kernels, "direct_all" | "direct" | "gemm" | None = the default
         # ops/f32.py CONV2_IMPL_F32, set by the same-session A/B of tools/f32_conv_ab.py; conv1_impl: conv1's
-        # backward, "direct" | "gemm" | None = CONV1_IMPL_F32, likewise
+        # backward, "direct" | "gemm" | None = CONV1_IMPL_F32, likewise; fc_impl: the fc stack, "fused" | "gemm" | None =
+        # FC_IMPL_F32, likewise
         self.model = build_model(model, seed=seed, relu_logits=relu_logits, flat=flat_params,
                                  backend=backend, fused=fused, conv2_impl=conv2_impl,
-                                 conv1_impl=conv1_impl).to(self.device)
+                                 conv1_impl=conv1_impl, fc_impl=fc_impl).to(self.device)
         self.B = int(batch_size)
         self.data = data.to(self.device)
         self.labels = labels.to(self.device).long()

@@ -3,10 +3,10 @@ from .cifar_cnn import CifarCNN, PARAM_SPECS, FLAT_SIZE, NUM_PARAMS  # noqa: F40
 
 
 def build_model(name: str, seed: int = 0, relu_logits: bool = True, flat=None, backend: str = "torch",
-                fused: bool = True, conv2_impl=None, conv1_impl=None):
+                fused: bool = True, conv2_impl=None, conv1_impl=None, fc_impl=None):
     if name in ("cifar_cnn", "cnn", "cifar10_cnn"):
         return CifarCNN(flat=flat, relu_logits=relu_logits, seed=seed, backend=backend, fused=fused,
-                        conv2_impl=conv2_impl, conv1_impl=conv1_impl)
+                        conv2_impl=conv2_impl, conv1_impl=conv1_impl, fc_impl=fc_impl)
     if backend != "torch":
         raise ValueError(f"backend {backend!r} exists for the CIFAR CNN only")
     if name in ("resnet20", "resnet-20"):

@@ -164,7 +164,7 @@ class CifarCNN(nn.Module):
 
     def __init__(self, flat: torch.Tensor | None = None, relu_logits: bool = True, seed: int = 0,
                  backend: str = "torch", fused: bool = True, conv2_impl: str | None = None,
-                 conv1_impl: str | None = None):
+                 conv1_impl: str | None = None, fc_impl: str | None = None):
         super().__init__()
         if backend not in ("torch", "hip_f32"):
             raise ValueError(f"unknown CNN backend {backend!r}")
@@ -183,6 +183,11 @@ class CifarCNN(nn.Module):
         if conv1_impl not in (None, "direct", "gemm"):
             raise ValueError(f"unknown conv1_impl {conv1_impl!r}")
         self.conv1_impl = conv1_impl
+        # fc_impl (that backend only): the fc stack, "fused" (csrc/kernels/f32_fc.hip) | "gemm" | None (ops/f32.py
+        # FC_IMPL_F32)
+        if fc_impl not in (None, "fused", "gemm"):
+            raise ValueError(f"unknown fc_impl {fc_impl!r}")
+        self.fc_impl = fc_impl
         if flat is None:
             g = torch.Generator().manual_seed(seed)
             flat = init_flat_params(g)
@@ -196,7 +201,7 @@ class CifarCNN(nn.Module):
         if self.backend == "hip_f32":
             from ..ops.f32 import cnn_forward_f32, flat_views
             return cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), self.relu_logits, self.fused,
-                                   self.conv2_impl, self.conv1_impl)
+                                   self.conv2_impl, self.conv1_impl, self.fc_impl)
         return cnn_forward(images_nhwc, self.params(), self.relu_logits)
 
     def loss_and_hits(self, images_nhwc: torch.Tensor, labels: torch.Tensor):
@@ -207,7 +212,7 @@ class CifarCNN(nn.Module):
             raise ValueError("loss_and_hits is the hip_f32 backend's loss head")
         from ..ops.f32 import cnn_forward_f32, flat_views, xent_head
         raw = cnn_forward_f32(images_nhwc, flat_views(self.flat, self.specs), False, self.fused, self.conv2_impl,
-                              self.conv1_impl)
+                              self.conv1_impl, self.fc_impl)
         return xent_head(raw, labels.view(-1), self.relu_logits)
 
     def named_tf_variables(self) -> Dict[str, torch.Tensor]:

@@ -27,7 +27,14 @@ element (255 = masked by the ReLU), the only thing the backward keeps, and the b
 at the conv output in one gather pass (no zero-fill, no atomics) -- and ``xent_head`` is the softmax
 cross-entropy, the batch's hit count and dlogits in one launch.  The forward is bit-identical to the PyTorch
 ops; the backward differs by the order of at most four addends per element.  ``cnn_forward_f32(fused=False)``
-keeps ``torch.relu`` + ``max_pool2d`` as the reference path; the two small fc ReLUs are PyTorch ops either way.
+keeps ``torch.relu`` + ``max_pool2d`` as the reference path.
+
+The fully connected stack has a kernel family of its own (csrc/kernels/f32_fc.hip, ``FC_IMPL_F32`` / ``fc_impl`` =
+"fused"): one autograd function ``_FcStack`` whose forward is fc1 on ``f32_gemm`` with the ReLU in its split-K
+reduction plus ONE launch of ``f32_fc_tail_fwd`` (fc2 + ReLU + fc3), and whose backward is ``f32_fc_tail_bwd`` (both
+ReLU-masked data gradients) and ``f32_fc_grads`` (the three weight gradients, their bias gradients as the last row
+of each [in + 1, out] result, and the gradient at the stack's input) -- no PyTorch op and no column-sum launch in
+between.  "gemm" keeps the chain of ``_Linear`` GEMMs with ``torch.relu`` between them.
 
 Inference and evaluation have a kernel of their own: ``cnn_infer_f32`` runs the whole eval-mode forward,
 uint8 pixels to fp32 logits, predictions and hit flags, in ONE launch of ``k_cnn_infer_f32``
@@ -218,6 +225,55 @@ def linear(x, w, b):
     return _Linear.apply(x, w, b)
 
 
+# The fc stack of the fp32 step: "fused" (csrc/kernels/f32_fc.hip: fc1's forward on the GEMM with its ReLU epilogue,
+# then one launch each for the forward tail, the backward tail and all gradients) or "gemm" (three _Linear GEMM
+# chains, f32_colsum and the PyTorch ReLUs); under the rule at CONV2_IMPL_F32 on tools/f32_conv_ab.py --stage fc
+# (profiles/f32_fc_ab.txt, B = 256: 0.411 ms/step fused against 0.498 ms gemm, spreads 0.008 / 0.007; B = 128: 0.350
+# against 0.433 ms, spreads 0.072 / 0.012)
+FC_IMPL_F32 = "fused"
+FC_IMPLS = ("fused", "gemm")
+
+
+def _fc_impl(impl: Optional[str]) -> str:
+    if impl not in (None,) + FC_IMPLS:
+        raise ValueError(f"fc_impl must be one of {FC_IMPLS} or None, got {impl!r}")
+    return impl or FC_IMPL_F32
+
+
+class _FcStack(torch.autograd.Function):
+    """logits = relu(relu(x W1 + b1) W2 + b2) W3 + b3 for the model's 2304 -> 384 -> 192 -> 10 (weights [in, out]).
+    Saves x, h1, h2; the backward is one call each of f32_fc_tail_bwd and f32_fc_grads."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3):
+        ops = _ops()
+        x, w1, w2, w3 = x.contiguous(), w1.contiguous(), w2.contiguous(), w3.contiguous()
+        h1 = ops.f32_gemm(x, w1, b1.contiguous(), False, False, True)
+        h2, logits = ops.f32_fc_tail_fwd(h1, w2, b2.contiguous(), w3, b3.contiguous())
+        ctx.save_for_backward(x, h1, h2, w1, w2, w3)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, h1, h2, w1, w2, w3 = ctx.saved_tensors
+        ops = _ops()
+        dlogits = dlogits.contiguous()
+        dh2, dh1 = ops.f32_fc_tail_bwd(dlogits, h1, h2, w2, w3)
+        g1, g2, g3, dx = ops.f32_fc_grads(x, h1, h2, dh1, dh2, dlogits, w1, ctx.needs_input_grad[0])
+        return dx, g1[:2304], g1[2304], g2[:384], g2[384], g3[:192], g3[192]
+
+
+def fc_stack(x, p: Dict[str, torch.Tensor], impl: Optional[str] = None):
+    """The three fc layers on x [B, 2304] -> the fc3 output [B, 10]; ``impl``: "fused" | "gemm" | None (``FC_IMPL_F32``)."""
+    w = [p[f"full_{k}_{i}"] for i in (1, 2, 3) for k in ("weight", "bias")]
+    if _fc_impl(impl) == "fused" and tuple(x.shape[1:]) == (2304,) \
+            and [tuple(t.shape) for t in w] == [(2304, 384), (384,), (384, 192), (192,), (192, 10), (10,)]:
+        return _FcStack.apply(x, *w)
+    x = torch.relu(linear(x, w[0], w[1]))
+    x = torch.relu(linear(x, w[2], w[3]))
+    return linear(x, w[4], w[5])
+
+
 def conv_same(x, w, b, implicit: bool = True, impl: Optional[str] = None, conv1_impl: Optional[str] = None):
     """``conv1_impl``: "direct" | "gemm" | None (``CONV1_IMPL_F32``) -- the weight-gradient kernel of the
     [B,24,24,3] -> 64 geometry (conv1) on the implicit path.  ``impl``: "direct_all" | "direct" | "gemm" | None (``CONV2_IMPL_F32``) -- the kernels of the
@@ -376,17 +432,17 @@ def _conv_stage(x, w, b, fused: bool, impl: Optional[str] = None, conv1_impl: Op
 
 def cnn_forward_f32(images_nhwc: torch.Tensor, p: Dict[str, torch.Tensor], relu_logits: bool = True,
                     fused: bool = True, conv2_impl: Optional[str] = None,
-                    conv1_impl: Optional[str] = None) -> torch.Tensor:
+                    conv1_impl: Optional[str] = None, fc_impl: Optional[str] = None) -> torch.Tensor:
     """The reference CNN (models/cifar_cnn.py:cnn_forward semantics) on the fp32 HIP kernels.  ``fused``:
     ReLU + pool of the conv stages through ``relu_pool`` where the geometry is one of its two ([B,24,24,64],
     [B,12,12,64]); otherwise, and with ``fused=False``, the PyTorch ops (same logits bit for bit).
     ``conv2_impl``: the second stage's conv kernel, ``conv_same``'s ``impl`` (independent of ``fused``); ``conv1_impl``: the
-    first stage's backward, "direct" | "gemm" | None (``CONV1_IMPL_F32``)."""
+    first stage's backward, "direct" | "gemm" | None (``CONV1_IMPL_F32``); ``fc_impl``: the fc stack, "fused" | "gemm" |
+    None (``FC_IMPL_F32``)."""
+    _fc_impl(fc_impl)
     x = images_nhwc.float().contiguous()
     x = _conv_stage(x, p["conv1_kernel"], p["conv1_bias"], fused, conv1_impl=conv1_impl)
     x = _conv_stage(x, p["conv2_kernel"], p["conv2_bias"], fused, conv2_impl)
     x = x.reshape(x.shape[0], -1)                               # NHWC flatten (cifar10cnn.py:126)
-    x = torch.relu(linear(x, p["full_weight_1"], p["full_bias_1"]))
-    x = torch.relu(linear(x, p["full_weight_2"], p["full_bias_2"]))
-    x = linear(x, p["full_weight_3"], p["full_bias_3"])
+    x = fc_stack(x, p, fc_impl)
     return torch.relu(x) if relu_logits else x

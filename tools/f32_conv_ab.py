@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the fp32 HIP training step on ONE GPU with conv2 on its direct kernels (csrc/kernels/f32_conv.hip)
 against the same step with conv2 on the implicit GEMM:
-   python tools/f32_conv_ab.py [--stage conv2|conv1] [--batches 256,128] [--steps 300] [--rounds 3] [--out FILE]
+   python tools/f32_conv_ab.py [--stage conv2|conv1|fc] [--batches 256,128] [--steps 300] [--rounds 3] [--out FILE]
 Per batch size, one hip_f32 EagerTrainer per path on the same synthetic data and seed -- conv2_impl="gemm",
 "direct" (forward and data gradient on k_f32_conv2) and "direct_all" (the weight gradient on
 k_f32_conv2_wgrad as well) --, all graph-captured; after warm-up, --steps steps per path are timed in
@@ -14,7 +14,10 @@ too.  Prints one JSON line per measurement and a summary line per batch size, an
 B = 256.
 --stage conv1 times conv1's backward instead (conv2 on its default): conv1_impl="gemm" (f32_relu_pool_bwd + the
 implicit GEMM) against "direct" (one launch of k_f32_conv1_wgrad, csrc/kernels/f32_conv1.hip); ops/f32.py
-CONV1_IMPL_F32 follows its "direct_wins_beyond_spread" at B = 256."""
+CONV1_IMPL_F32 follows its "direct_wins_beyond_spread" at B = 256.
+--stage fc times the fc stack (the convs on their defaults): fc_impl="gemm" (the _Linear GEMM chain, f32_colsum and the
+PyTorch ReLUs) against "fused" (csrc/kernels/f32_fc.hip); ops/f32.py FC_IMPL_F32 follows its
+"fused_wins_beyond_spread" at B = 256."""
 import argparse
 import json
 import os
@@ -27,7 +30,8 @@ import torch  # noqa: E402
 import dmlc  # noqa: E402,F401
 from dmlc.engine.eager import EagerTrainer  # noqa: E402
 
-STAGES = {"conv2": ("conv2_impl", ("gemm", "direct", "direct_all")), "conv1": ("conv1_impl", ("gemm", "direct"))}
+STAGES = {"conv2": ("conv2_impl", ("gemm", "direct", "direct_all")), "conv1": ("conv1_impl", ("gemm", "direct")),
+          "fc": ("fc_impl", ("gemm", "fused"))}
 
 
 def run(batch, steps, rounds, data, labels, stage="conv2"):
@@ -57,8 +61,8 @@ def run(batch, steps, rounds, data, labels, stage="conv2"):
     out = {"batch": batch, "stage": stage, "dtype": "fp32", "steps": steps, "rounds": rounds, "graph": True,
            "ms_per_step_by_round": per_round, "min_ms_per_step": best, "spread_ms": spread,
            "images_per_s": {k: round(batch / v * 1e3) for k, v in best.items()},
-           "speedup_direct_over_gemm": round(best["gemm"] / best["direct"], 3),
-           "direct_wins_beyond_spread": best["gemm"] - best["direct"] > max(spread["gemm"], spread["direct"])}
+           f"speedup_{PATHS[1]}_over_gemm": round(best["gemm"] / best[PATHS[1]], 3),
+           f"{PATHS[1]}_wins_beyond_spread": best["gemm"] - best[PATHS[1]] > max(spread["gemm"], spread[PATHS[1]])}
     if stage == "conv2":
         out.update({"speedup_direct_all_over_direct": round(best["direct"] / best["direct_all"], 3),
                     "direct_all_wins_beyond_spread":

@@ -198,3 +198,12 @@ def conv1_dy_reads(off):
 print("conv1 wgrad x reads (mean, worst passes): pitch 84 ->", conv1_x_reads(84), " pitch 88 ->", conv1_x_reads(88))
 print("conv1 wgrad dy reads (mean, worst passes): [pixel][64] ->", conv1_dy_reads(lambda p, nt, r: p * 64 + 16 * nt + r),
       " channel-tile planes ->", conv1_dy_reads(lambda p, nt, r: nt * 2320 + p * 16 + r))
+
+
+# --- fp32 fc tail kernels (f32_fc.hip fc_core): ds_read_b128 of A[r][k0 + 4 q .. + 3] from a [16][pitch] fp32 tile ---
+def fc_tail_reads(pitch):
+    return cycles_g([4 * ((l & 15) * pitch + 4 * (l >> 4)) for l in range(64)], G128, 4)
+
+
+print("fc tail A-tile b128 reads (cycles, 4 = conflict-free):",
+      ", ".join(f"pitch {p} -> {fc_tail_reads(p)}" for p in (384, 388, 196, 400, 404)))
